@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - Msamples/s of the Harmonic + FilteredNoise hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`, one
@@ -14,17 +14,22 @@ One "step" = one pass of the hot path over one batch of synthetic control tensor
 each output sample counted once.  Inputs are resident in HBM before the timed region.
 Workload (per GPU, weak scaling): the shape BASELINE.json's metric and target are quoted on - batch 128 of
 configs[1]'s clips: 4 s @ 16 kHz, F=1000 frames, K=100 harmonics (all below Nyquist: f0 = 70 + N(0,1) Hz), M=65
-noise bands.  configs[1] itself (batch 32) is timed the same way right after and reported as `configs_1`.
+noise bands.  With --full, configs[1] itself (batch 32) is timed the same way right after and reported as `configs_1`.
 
 Timing.  After W warm-up steps (and `--settle` seconds of untimed load: clock settle) the region "exactly K steps, barrier +
-torch.cuda.synchronize() on both sides" is run `--repeats` times (>= 10 by default).  Each region is timed
-twice: by the host clock around the bracket, and by HIP events recorded on the stream(s) at its first and after
-its last launch (the two-stream mode forks from / joins into the base stream with events).  `ms_per_step` and
-`value` are the MEDIAN event-timed region (max over ranks) - at the driver's K = 20 a region is under a
-millisecond and the host-side synchronize alone is 2-8 % of it; the host-clock median and the first region are
-reported beside it (`timing`).
+torch.cuda.synchronize() on both sides" is run `--repeats` times: once in a plain run - exactly K timed steps -, >= 10 times
+with --full.  Each region is timed twice: by the host clock around the bracket, and by HIP events recorded on the stream(s) at
+its first and after its last launch (the two-stream mode forks from / joins into the base stream with events).  `ms_per_step`
+and `value` are the (median) event-timed region (max over ranks) - at K = 20 a region is under a millisecond and the host-side
+synchronize alone is 2-8 % of it; the host clock is reported beside it (`timing`).
 
-The JSON line also carries
+--dump-outputs DIR writes what the last timed step returned - the Harmonic and FilteredNoise audio, DIR/harmonic.npy and
+DIR/filtered_noise.npy, float32 (a fixed, seeded sample of rows when both would exceed DUMP_BUDGET_BYTES; the line's
+`dumped_outputs` names the rows).  The inputs are seeded and the noise generator's call counter is rewound before the timed
+steps, so the same arguments write the same arrays in every run.
+
+A plain run does only that: set up, warm up, time the K steps, dump, print the line (metric, value, unit, ms_per_step, dtype,
+config, the whole-step HBM fraction, timing).  With --full the JSON line also carries
   roofline         : dominant kernel, algorithmic bytes per launch / its mean duration measured
                      with HIP events on the launch stream during the timed regions (ddsp_profile_*),
                      against the 8 TB/s HBM peak (the path is in fact ALU-bound).
@@ -47,6 +52,8 @@ The JSON line also carries
   cpu_baseline     : the numpy fp32 oracle ("port" of the TF op chain; TF itself cannot run
                      here) timed on this host's cores (concurrent worker processes) on a bounded
                      sample of the same workload.
+  and the isolated per-kernel times, `one_stream`, `fused_add`, the measured copy bandwidth, the f0 regimes and `shards`.
+  (--also-other-mode and --allgather are opt-ins of their own.)
 """
 import argparse
 import json
@@ -66,6 +73,8 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 DTYPE = ('f32 (Harmonic wavetables and the FilteredNoise FIR/IR products: 22-bit operands - fp16 hi/lo pairs on the MFMA matrix cores - '
          'with fp32 accumulation; everything else plain fp32, the frame phase prefix fp64)')
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all arrays together stay below this
+DUMP_SEED = 0                  # --dump-outputs: the rows kept when the outputs are larger than the budget
 
 
 def parse_args(argv=None):
@@ -77,9 +86,18 @@ def parse_args(argv=None):
                   help='seconds of untimed load after the W warm-up steps and before the timed regions: a fresh box reaches '
                        'its sustained clocks only after some tenths of a second (r03p: the same kernels 4 %% slower in a process '
                        'that timed its 20-step regions 50 ms after its first launch)')
-  ap.add_argument('--repeats', type=int, default=0,
-                  help='timed regions of K steps each (0: at least 10, more when a region is short, so that '
-                       'about 0.1 s is measured in all); the median is reported')
+  ap.add_argument('--repeats', type=int, default=None,
+                  help='timed regions of K steps each; the median is reported (default: one region - exactly K timed '
+                       'steps - in a plain run, 0 with --full; 0: at least 10, more when a region is short, so that '
+                       'about 0.1 s is measured in all)')
+  ap.add_argument('--full', action='store_true',
+                  help='everything beyond the headline: the per-kernel breakdown and roofline, the one-stream regions, the '
+                       'fused Add, the device-copy bandwidth and f0 regimes, configs_1 / configs_4 / configs_2 / configs_3 '
+                       'and the other noise resolution, the CPU baseline and the shard table (off: set up, warm up, time '
+                       'the K steps, print the line)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; a '
+                       'fixed, seeded sample of rows when the whole would exceed %d MB)' % (DUMP_BUDGET_BYTES >> 20))
   ap.add_argument('--batch', type=int, default=128,
                   help='clips per GPU (128: the shape the north-star target is quoted on; configs[1] has 32)')
   ap.add_argument('--n-frames', type=int, default=1000)
@@ -164,13 +182,16 @@ def cpu_baseline(a):
   workers actually used, the one-process figure is reported beside it).  The op chain is memory-bound (it
   materialises the [N, K] tensors as TF does), so more workers is not monotonically faster - measured on the
   2 x 64-core GPU host: 32 workers 10.5 Msamples/s, 128 workers 3.4.  With --cpu-procs 0 the leg therefore tries
-  32, 64 and the physical core count (each bounded by the cores there are) and reports the BEST as the baseline,
-  listing every count it tried."""
+  32, 64 and the physical core count (each bounded by the cores there are, and by OMP_NUM_THREADS where that is set) and
+  reports the BEST as the baseline, listing every count it tried."""
   from oracle import cpu_baseline as leg
   shape = (a.n_frames, a.n_harmonics, a.n_bands, a.n_samples, a.sample_rate, a.f0)
   if a.cpu_procs > 0:
     return leg.measure(a.cpu_clips, a.cpu_procs, *shape)
   top = leg.default_procs()
+  budget = os.environ.get('OMP_NUM_THREADS', '')
+  if budget.isdigit() and int(budget) > 0:       # a host that hands this job fewer cores than it has says so here
+    top = min(top, int(budget))
   tried, best = [], None
   for procs in sorted({min(32, top), min(64, top), top}):
     r = leg.measure(a.cpu_clips if procs <= 64 else max(2, a.cpu_clips // 2), procs, *shape)
@@ -269,10 +290,11 @@ def build_result(a, world, B, elapsed, prof, breakdown, dominant, overlap, aux=N
   total_samples = world * B * a.n_samples * a.steps
   value = total_samples / elapsed / 1e6
   harm_bytes, noise_bytes = algorithmic_bytes(a, B)
-  roof = kernel_roofline(a, B, dominant, *prof[dominant])
-  dom_flops, dom_avg_s = roof.pop('_flops'), roof.pop('_avg_s')
   step_bytes = harm_bytes + noise_bytes
   harm_flops, noise_flops = algorithmic_flops(a, B)
+  whole_step = {'algorithmic_bytes': step_bytes,
+                'achieved_GBs': step_bytes / (elapsed / a.steps) / 1e9,
+                'frac': step_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS}
   result = {
       'metric': 'Msamples/s (Harmonic+FilteredNoise, 16kHz, 100 harmonics)',
       'value': value, 'unit': 'Msamples/s', 'n_gpus': world, 'steps': a.steps,
@@ -291,26 +313,30 @@ def build_result(a, world, B, elapsed, prof, breakdown, dominant, overlap, aux=N
                      else 'one stream, back to back',
           'kernel_variants': {'harmonic': a.harm_kernel, 'filtered_noise': a.noise_kernel}},
       'per_gpu_value': value / world,
-      'roofline': dict(roof, **{
-          'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'event_stride': a.event_stride,
-          'timing': roofline_timing or ('dispatch start/stop events (hipExtLaunchKernelGGL) on the launch stream, '
-                                        'every event_stride-th launch inside the timed regions'),
-          'whole_step': {'algorithmic_bytes': step_bytes,
-                         'achieved_GBs': step_bytes / (elapsed / a.steps) / 1e9,
-                         'frac': step_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS},
-          # the path sits above the fp32 ridge point: the vector-ALU ceiling beside the HBM fraction - on the
-          # REFERENCE FORMULATION's flop count (3 FMAs per sample and live harmonic, 2 L per sample of the FIR).  The
-          # wavetable / matrix-core kernels do not execute those flops: the figure says how fast a direct-sum kernel would
-          # have to run to keep up, not what this one achieves (VERDICT r3, weak #6b); what it executes is `executed`
-          'alu_note': {'reference_formulation_flop_per_launch': dom_flops,
-                       'reference_formulation_equivalent_TFLOPs': dom_flops / dom_avg_s / 1e12,
-                       'peak_TFLOPs': FP32_VECTOR_PEAK_TFLOPS,
-                       'reference_formulation_equivalent_frac': dom_flops / dom_avg_s / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
-                       'whole_step_reference_formulation_equivalent_frac':
-                           (harm_flops + noise_flops) / (elapsed / a.steps) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
-                       'executed': load_issue_counters(a, dominant, B, dom_avg_s)}}),
-      'kernel_breakdown_us_isolated': {k: v[0] / v[1] * 1e3 for k, v in breakdown.items()},
+      # the whole step against the HBM peak is arithmetic on the headline; the dominant kernel's figures need the
+      # per-kernel runs of --full
+      'roofline': {'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'whole_step': whole_step},
   }
+  if dominant is not None:
+    roof = kernel_roofline(a, B, dominant, *prof[dominant])
+    dom_flops, dom_avg_s = roof.pop('_flops'), roof.pop('_avg_s')
+    result['roofline'] = dict(roof, **{
+        'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'event_stride': a.event_stride,
+        'timing': roofline_timing or ('dispatch start/stop events (hipExtLaunchKernelGGL) on the launch stream, '
+                                      'every event_stride-th launch inside the timed regions'),
+        'whole_step': whole_step,
+        # the path sits above the fp32 ridge point: the vector-ALU ceiling beside the HBM fraction - on the
+        # REFERENCE FORMULATION's flop count (3 FMAs per sample and live harmonic, 2 L per sample of the FIR).  The
+        # wavetable / matrix-core kernels do not execute those flops: the figure says how fast a direct-sum kernel would
+        # have to run to keep up, not what this one achieves (VERDICT r3, weak #6b); what it executes is `executed`
+        'alu_note': {'reference_formulation_flop_per_launch': dom_flops,
+                     'reference_formulation_equivalent_TFLOPs': dom_flops / dom_avg_s / 1e12,
+                     'peak_TFLOPs': FP32_VECTOR_PEAK_TFLOPS,
+                     'reference_formulation_equivalent_frac': dom_flops / dom_avg_s / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
+                     'whole_step_reference_formulation_equivalent_frac':
+                         (harm_flops + noise_flops) / (elapsed / a.steps) / 1e12 / FP32_VECTOR_PEAK_TFLOPS,
+                     'executed': load_issue_counters(a, dominant, B, dom_avg_s)}})
+    result['kernel_breakdown_us_isolated'] = {k: v[0] / v[1] * 1e3 for k, v in breakdown.items()}
   if timing:
     result['timing'] = timing
     if 'host_clock_ms_per_step_median' in timing:           # the clock round 1's headline used: comparable across rounds
@@ -363,9 +389,9 @@ def build_result(a, world, B, elapsed, prof, breakdown, dominant, overlap, aux=N
         'value': world * B * a.n_samples * a.steps / alt_elapsed / 1e6}
   if gather_ms is not None:
     result['allgather_ms'] = gather_ms
-  if not a.no_cpu_baseline and world == 1:
+  if a.full and not a.no_cpu_baseline and world == 1:
     result['cpu_baseline'] = cpu_baseline_fn(a)
-  elif not a.no_cpu_baseline:
+  elif a.full and not a.no_cpu_baseline:
     result['cpu_baseline'] = None     # rank 0 at N=1 only (bench contract)
   if a.dry_run:
     result.update(dry_run=True, data='none (dry run: no device work; plumbing test only, not a measurement)')
@@ -378,6 +404,25 @@ def shape_name(B):
   if B == 32:
     return 'BASELINE configs[1]'
   return 'configs[1] clips at another batch size'
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+  """--dump-outputs: what a caller of the timed path received from its last step, as DIR/<name>.npy in float32.  The
+  arrays share their first (batch) axis; when together they would exceed `budget` bytes, the same seeded sample of rows
+  is kept of each, in ascending order.  -> {name: {'file', 'shape' (before sampling), 'rows' ('all' or the rows kept)}}."""
+  os.makedirs(directory, exist_ok=True)
+  host = {name: np.asarray(x.detach().cpu().numpy() if hasattr(x, 'detach') else x, dtype=np.float32)
+          for name, x in arrays.items()}
+  rows = None
+  if sum(x.nbytes for x in host.values()) > budget:
+    n = min(x.shape[0] for x in host.values())
+    row_bytes = sum(x[0].nbytes for x in host.values())
+    rows = np.sort(np.random.default_rng(seed).choice(n, max(1, min(n, budget // row_bytes)), replace=False))
+  info = {}
+  for name, x in host.items():
+    np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(x if rows is None else x[rows]))
+    info[name] = {'file': name + '.npy', 'shape': list(x.shape), 'rows': 'all' if rows is None else rows.tolist()}
+  return info
 
 
 def second_block(a, world, B, elapsed, steps, prof, breakdown, elapsed_one_stream=None):
@@ -489,6 +534,7 @@ def main(argv=None):
       def step(two_streams=None):
         time.sleep(2e-4)
         return out
+      step.rewind = lambda: None
       return step, {}
   else:
     from ddsp_amd import build
@@ -535,7 +581,13 @@ def main(argv=None):
       def step_fused_add(two_streams=None):
         z = fnoise(dev['magnitudes'])
         return harmonic.call_add(dev['amplitudes'], dev['harmonic_distribution'], dev['f0_hz'], z), z
+
+      def rewind():
+        # the generated noise is keyed by (seed, call counter) and the clock settle runs for a time, not a count: back to
+        # call 0 before the timed steps, so that they draw the same noise - and compute the same outputs - in every run
+        fnoise._calls = 0
       step.fused_add = step_fused_add
+      step.rewind = rewind
       return step, dev
 
   def sync_all():
@@ -614,11 +666,12 @@ def main(argv=None):
   if not dry:
     torch.cuda.synchronize()
 
-  # diagnostic pass (untimed, one stream so every kernel runs alone): every kernel bracketed, to
+  # diagnostic pass (--full; untimed, one stream so every kernel runs alone): every kernel bracketed, to
   # find the dominant one and give the isolated per-kernel times
-  if dry:
+  breakdown, dominant = None, None
+  if a.full and dry:
     breakdown = {'dry_run_step': (0.6, 3)}
-  else:
+  elif a.full:
     for _ in range(5):               # the first one-stream launches after the two-stream phase are not representative
       step(two_streams=False)
     torch.cuda.synchronize()
@@ -627,7 +680,8 @@ def main(argv=None):
       step(two_streams=False)
     torch.cuda.synchronize()
     breakdown = _lib.profile_end()
-  dominant = max(breakdown, key=lambda k: breakdown[k][0] / breakdown[k][1])
+  if breakdown is not None:
+    dominant = max(breakdown, key=lambda k: breakdown[k][0] / breakdown[k][1])
   # clock settle LAST, in the issue mode of the timed regions: the first two-stream regions after a stretch of one-stream
   # launches (the diagnostic pass) are slow - 3.4 ms for a 1.4 ms region, then tens of regions above the steady 68-69 us per
   # step (r03t: 74.2 vs 70.0 us as the median of 29 / 71 regions) - the runtime re-activates the second stream's queue
@@ -642,22 +696,31 @@ def main(argv=None):
     timed_region(step, k_warm, overlap)
 
   # ---- timed regions: exactly K steps each, barrier + synchronize on both sides --------------------------
-  e_probe, _, _ = timed_region(step, a.steps, overlap)          # untimed probe: sizes the repeat count
-  e_probe = max_over_ranks(e_probe)                             # every rank must run the SAME number of regions (collectives inside)
-  repeats = a.repeats if a.repeats > 0 else int(min(200, max(10, 0.1 / max(e_probe, 1e-6))))
+  # (a plain run times ONE region: exactly K timed steps; --full keeps the median of >= 10)
+  repeats = a.repeats if a.repeats is not None else (0 if a.full else 1)
+  if repeats <= 0:
+    e_probe, _, _ = timed_region(step, a.steps, overlap)          # untimed probe: sizes the repeat count
+    e_probe = max_over_ranks(e_probe)                             # every rank must run the SAME number of regions (collectives inside)
+    repeats = int(min(200, max(10, 0.1 / max(e_probe, 1e-6))))
   # The dominant kernel's dispatch events.  At configs[1]'s batch they are sampled inside the timed regions.  At batch 128
   # on two streams a dispatch of one kernel also spans the time its blocks wait for the CUs the other kernel's persistent
   # blocks still hold, so its duration says nothing about the kernel: there the events are sampled in one-stream regions
   # of the same K steps run right after the timed ones (their step time is reported as `one_stream`).
   events_in_one_stream_regions = overlap and B >= 64
-  if not dry and not events_in_one_stream_regions:
+  if a.full and not dry and not events_in_one_stream_regions:
     _lib.profile_begin([dominant], max_records=2 * a.steps * repeats // max(a.event_stride, 1) + 64,
                        stride=a.event_stride)
+  step.rewind()
   ev, wall, out = repeated_regions(step, a.steps, overlap, repeats)
-  prof = {dominant: (0.6, 3)} if dry else (None if events_in_one_stream_regions else _lib.profile_end())
+  prof = None
+  if a.full:
+    prof = {dominant: (0.6, 3)} if dry else (None if events_in_one_stream_regions else _lib.profile_end())
   elapsed = max_over_ranks(statistics.median(ev))
+  dumped = None
+  if a.dump_outputs and rank == 0:       # what the caller of the path received from the last timed step
+    dumped = dump_outputs(a.dump_outputs, {'harmonic': out[0], 'filtered_noise': out[1]})
   one_stream_elapsed, roofline_timing = None, None
-  if events_in_one_stream_regions:
+  if a.full and events_in_one_stream_regions:
     reps1 = max(3, repeats // 3)
     if not dry:
       _lib.profile_begin([dominant], max_records=2 * a.steps * reps1 // max(a.event_stride, 1) + 64,
@@ -669,9 +732,9 @@ def main(argv=None):
     roofline_timing = ('dispatch start/stop events (hipExtLaunchKernelGGL) on the launch stream, every event_stride-th '
                        'launch inside %d one-stream regions of the same K steps run right after the timed (two-stream) '
                        'regions: on two streams a dispatch also spans the wait for the CUs the other kernel holds' % reps1)
-  timing = {'method': 'median of %d regions of K=%d steps; each region bracketed by barrier + synchronize and '
+  timing = {'method': '%s K=%d steps; each region bracketed by barrier + synchronize and '
                       'timed by HIP events on the stream(s) (value) and by the host clock (beside it)' %
-                      (repeats, a.steps),
+                      ('one region of' if repeats == 1 else 'median of %d regions of' % repeats, a.steps),
             'repeats': repeats, 'region_ms_median': statistics.median(ev) * 1e3,
             'region_ms_min': min(ev) * 1e3, 'region_ms_max': max(ev) * 1e3, 'region_ms_first': ev[0] * 1e3,
             'host_clock_ms_per_step_median': max_over_ranks(statistics.median(wall)) / a.steps * 1e3,
@@ -685,7 +748,7 @@ def main(argv=None):
 
   # ---- Harmonic + FilteredNoise + Add as the DAGs run it, the Add fused into the Harmonic kernel (one stream) ----
   fused_add_elapsed = None
-  if not dry and not a.no_aux and hasattr(step, 'fused_add'):
+  if a.full and not dry and not a.no_aux and hasattr(step, 'fused_add'):
     # (as the configs_1 block: what may raise runs inside the `try`, the ranks agree on the outcome, and the regions - which
     # hold a barrier each when world > 1 - run outside it on every rank or on none: a rank that raised in the middle of a
     # loop of regions would leave the others waiting in a barrier and cost the headline line)
@@ -704,7 +767,7 @@ def main(argv=None):
 
   # ---- auxiliary yardsticks (untimed for the headline; a failure here never costs the JSON line) ----
   aux = {}
-  if not a.no_aux and not dry:
+  if a.full and not a.no_aux and not dry:
     try:
       # (i) SURVEY.md 8(d): the fraction is quoted against the 8 TB/s spec peak; the device-to-device copy
       # rate measured in the same run says what this box's HBM actually sustains (read + write counted)
@@ -763,7 +826,7 @@ def main(argv=None):
   # (every rank takes the same path through the collectives: a failure on one rank is agreed on before anything is
   # reduced over the ranks - ADVICE r2)
   second = None
-  if not a.no_second_shape and a.second_batch > 0 and a.second_batch != B:
+  if a.full and not a.no_second_shape and a.second_batch > 0 and a.second_batch != B:
     BN = a.second_batch
     ns_steps = max(10, min(a.steps, 200))
     err, med_n, med_1, prof_n, bd_n = None, 0.0, 0.0, None, {}
@@ -805,7 +868,7 @@ def main(argv=None):
   # 129 .. 200 harmonics; same definitions as `configs_1`)
   fifth = None
   default_shape = (a.n_frames, a.n_harmonics, a.n_samples, a.sample_rate, a.n_bands) == (1000, 100, 64000, 16000, 65)
-  if second is not None and 'error' not in second and default_shape and not a.no_aux:
+  if a.full and second is not None and 'error' not in second and default_shape and not a.no_aux:
     a5 = argparse.Namespace(**vars(a))
     a5.n_frames, a5.n_harmonics, a5.n_samples, a5.sample_rate = 2500, 200, 480000, 48000
     c5_steps = 50                                 # (its own region length: a 146 us step; three untimed regions first)
@@ -886,7 +949,7 @@ def main(argv=None):
                 kernel_launches_per_step={k: v[1] / 5.0 for k, v in bd.items()})
 
   other = {}
-  if default_shape and not dry and not a.no_aux and not a.no_other_configs:
+  if a.full and default_shape and not dry and not a.no_aux and not a.no_other_configs:
     BO = 128
     synth_bytes = 4 * BO * (a.n_frames * (a.n_harmonics + 2) + a.n_frames * a.n_bands + a.n_samples)   # the DAG with Add fused: one [B,N] stream
 
@@ -1010,21 +1073,22 @@ def main(argv=None):
   # configurations at this world size (weak scaling: per-GPU batch x world; configs[3] 1024 -> 128 and configs[4] 256 -> 32
   # at 8 GPUs), summed into one vector: rank 0 prints what every rank actually took (tests/test_bench_contract.py, 8 ranks)
   shards = None
-  try:
-    from ddsp_amd.distributed import shard_bounds
-    plan = {'headline': B * world, 'configs_3': 128 * world, 'configs_4': 32 * world}
-    v = [0.0] * (len(plan) * 2 * world)
-    for i, (name, gb) in enumerate(plan.items()):
-      v[(i * world + rank) * 2], v[(i * world + rank) * 2 + 1] = (float(x) for x in shard_bounds(gb, rank, world))
-    if world > 1:
-      vec = torch.tensor(v, dtype=torch.float64, device=dev_name)
-      dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-      v = vec.tolist()
-    v = [int(x) for x in v]
-    shards = {name: {'global_batch': gb, 'rows_of_rank': [[v[(i * world + r) * 2], v[(i * world + r) * 2 + 1]] for r in range(world)]}
-              for i, (name, gb) in enumerate(plan.items())}
-  except ImportError:
-    pass
+  if a.full:
+    try:
+      from ddsp_amd.distributed import shard_bounds
+      plan = {'headline': B * world, 'configs_3': 128 * world, 'configs_4': 32 * world}
+      v = [0.0] * (len(plan) * 2 * world)
+      for i, (name, gb) in enumerate(plan.items()):
+        v[(i * world + rank) * 2], v[(i * world + rank) * 2 + 1] = (float(x) for x in shard_bounds(gb, rank, world))
+      if world > 1:
+        vec = torch.tensor(v, dtype=torch.float64, device=dev_name)
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+        v = vec.tolist()
+      v = [int(x) for x in v]
+      shards = {name: {'global_batch': gb, 'rows_of_rank': [[v[(i * world + r) * 2], v[(i * world + r) * 2 + 1]] for r in range(world)]}
+                for i, (name, gb) in enumerate(plan.items())}
+    except ImportError:
+      pass
 
   if rank == 0:
     result = build_result(a, world, B, elapsed, prof, breakdown, dominant, overlap, aux, alt_elapsed, gather_ms,
@@ -1035,6 +1099,8 @@ def main(argv=None):
     result.update(other)
     if shards:
       result['shards'] = shards
+    if dumped:
+      result['dumped_outputs'] = dumped
     print(json.dumps(result), flush=True)
 
   if world > 1:

@@ -43,7 +43,7 @@ def test_defaults_are_the_north_star_shape(bench):
 
 @pytest.mark.parametrize('world,batch,dominant', [(1, 32, 'noise_fused65_kernel'), (8, 128, 'harm_table_kernel')])
 def test_json_line_fields_and_roofline_arithmetic(bench, world, batch, dominant):
-  a = _args(bench, '--gpus', str(world), '--batch', str(batch), '--steps', '1000', '--warmup', '500')
+  a = _args(bench, '--gpus', str(world), '--batch', str(batch), '--steps', '1000', '--warmup', '500', '--full')
   elapsed = 0.0368 if batch == 32 else 0.1172                       # seconds for 1000 steps (profiles/r01_bench_*)
   launch_us = 31.0 if batch == 32 else 59.96
   prof = {dominant: (launch_us * 125 * 1e-3, 125)}
@@ -187,7 +187,7 @@ def test_main_control_flow_with_the_gpu_mocked_out(bench, monkeypatch, capsys):
                                                         'kind': 'port', 'sample': 'stub'})
   monkeypatch.setenv('WORLD_SIZE', '1')
   monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '7', '--warmup', '2', '--batch', '2', '--n-frames', '10',
-                                    '--n-samples', '640', '--also-other-mode'])
+                                    '--n-samples', '640', '--also-other-mode', '--full'])
   bench.main()
   out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')]
   assert len(out) == 1                                               # ONE JSON line
@@ -320,7 +320,7 @@ def test_main_multi_rank_branches_with_device_and_collectives_mocked_out(bench, 
   for key, value in (('WORLD_SIZE', '2'), ('RANK', '0'), ('LOCAL_RANK', '0')):
     monkeypatch.setenv(key, value)
   monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '2',
-                                    '--n-frames', '10', '--n-samples', '640', '--allgather'])
+                                    '--n-frames', '10', '--n-samples', '640', '--allgather', '--full'])
   bench.main()
   out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')]
   assert len(out) == 1
@@ -342,7 +342,7 @@ def test_main_other_configs_blocks_with_the_device_mocked_out(bench, monkeypatch
   calls = {}
   _mock_device(monkeypatch, bench, calls)
   monkeypatch.setenv('WORLD_SIZE', '1')
-  monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '3', '--warmup', '1', '--settle', '0'])
+  monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '3', '--warmup', '1', '--settle', '0', '--full'])
   bench.main()
   out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')]
   assert len(out) == 1
@@ -365,6 +365,106 @@ def test_main_other_configs_blocks_with_the_device_mocked_out(bench, monkeypatch
   assert calls['noise_bits'] == {11, 23} and calls['loss'] > 10 and calls['reverb'] > 20 and calls['fused'] > 30
   assert calls['loss_kwargs'] == {'logmag_weight': 1.0}
   assert '2^23 levels' in line['config']['workload'] and 'noise_bits=23' in line['config']['workload']
+
+
+def test_plain_run_times_exactly_k_steps_and_only_the_headline(bench, monkeypatch, capsys):
+  """Without --full the run sets up, warms up, times exactly --steps steps in one region and prints the headline: no
+  diagnostic pass, no side blocks, no CPU leg (with the clock settle off every step called is a warm-up or a timed one)."""
+  calls = {}
+  _mock_device(monkeypatch, bench, calls)
+  monkeypatch.setattr(bench, 'cpu_baseline', lambda a: pytest.fail('the CPU leg is a --full block'))
+  monkeypatch.setenv('WORLD_SIZE', '1')
+  monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '7', '--warmup', '3', '--settle', '0'])
+  bench.main()
+  out = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')]
+  assert len(out) == 1
+  line = json.loads(out[0])
+  assert calls['harm'] == calls['noise'] == 3 + 7 and 'names' not in calls and 'fused' not in calls
+  for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'n_gpus'):
+    assert key in line, key
+  assert line['steps'] == 7 and line['warmup'] == 3 and line['timing']['repeats'] == 1
+  assert line['ms_per_step'] == pytest.approx(1.0 / 7)                 # the one region's event time (1 ms here) over K
+  assert line['value'] == pytest.approx(128 * 64000 * 7 / 1e-3 / 1e6) and line['unit'] == 'Msamples/s'
+  assert line['roofline']['whole_step']['frac'] > 0 and 'kernel' not in line['roofline']
+  for key in ('cpu_baseline', 'kernel_breakdown_us_isolated', 'configs_1', 'configs_2', 'configs_3', 'configs_4',
+              'fnoise_11_bit_levels', 'f0_regimes', 'fused_add', 'one_stream', 'shards', 'dumped_outputs'):
+    assert key not in line, key
+
+
+def test_dump_outputs_are_the_last_timed_step_and_the_same_from_run_to_run(bench, monkeypatch, capsys, tmp_path):
+  """--dump-outputs DIR: the two arrays the timed path returned from its last step, float32; the noise is keyed by a call
+  counter and the clock settle runs for a time, so the counter is rewound before the timed steps - two runs write the same."""
+  import numpy as np
+  import torch
+  import ddsp_amd
+  calls = {}
+  _mock_device(monkeypatch, bench, calls)
+
+  class _Harmonic:
+    def __init__(self, n_samples, sample_rate):
+      self.n = n_samples
+
+    def __call__(self, amplitudes, harmonic_distribution, f0_hz):
+      return amplitudes.mean(dim=(1, 2))[:, None] * torch.arange(self.n, dtype=torch.float32)
+
+  class _Noise:
+    def __init__(self, n_samples, window_size, seed, noise_bits=23):
+      self.n, self._calls = n_samples, 0
+
+    def __call__(self, magnitudes):
+      self._calls += 1
+      return magnitudes.mean(dim=(1, 2))[:, None] + torch.full((magnitudes.shape[0], self.n), float(self._calls))
+  monkeypatch.setattr(ddsp_amd.synths, 'Harmonic', _Harmonic)
+  monkeypatch.setattr(ddsp_amd.synths, 'FilteredNoise', _Noise)
+  monkeypatch.setenv('WORLD_SIZE', '1')
+  got = []
+  for run in ('a', 'b'):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '5', '--warmup', '2', '--settle', '0.02', '--batch', '3',
+                                      '--n-frames', '10', '--n-samples', '640', '--dump-outputs', str(tmp_path / run)])
+    bench.main()
+    line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')][0])
+    assert line['dumped_outputs']['harmonic'] == {'file': 'harmonic.npy', 'shape': [3, 640], 'rows': 'all'}
+    got.append({name: np.load(str(tmp_path / run / (name + '.npy'))) for name in ('harmonic', 'filtered_noise')})
+  x = bench.make_inputs(3, bench.parse_args(['--n-frames', '10']), seed=1000)
+  for name, arr in got[0].items():
+    assert arr.dtype == np.float32 and arr.shape == (3, 640)
+    np.testing.assert_array_equal(arr, got[1][name])
+  np.testing.assert_allclose(got[0]['harmonic'][:, 1], x['amplitudes'].mean(axis=(1, 2)), rtol=1e-6)
+  np.testing.assert_allclose(got[0]['filtered_noise'][:, 0] - x['magnitudes'].mean(axis=(1, 2)), 5.0, rtol=1e-6)   # call 5 of 5
+
+
+def test_dump_outputs_keeps_a_seeded_sample_of_rows_within_the_budget(bench, tmp_path):
+  import numpy as np
+  rng = np.random.default_rng(3)
+  arrays = {'harmonic': rng.standard_normal((10, 100)).astype(np.float32), 'filtered_noise': rng.standard_normal((10, 100))}
+  info = bench.dump_outputs(str(tmp_path / 'a'), arrays, budget=3000)
+  again = bench.dump_outputs(str(tmp_path / 'b'), arrays, budget=3000)
+  rows = info['harmonic']['rows']
+  assert info == again and rows == info['filtered_noise']['rows'] and rows == sorted(rows) and len(rows) == 3
+  total = 0
+  for name, x in arrays.items():
+    got = np.load(str(tmp_path / 'a' / (name + '.npy')))
+    assert got.dtype == np.float32 and info[name]['shape'] == [10, 100]
+    np.testing.assert_array_equal(got, x[rows].astype(np.float32))
+    total += got.nbytes
+  assert total <= 3000
+  assert bench.dump_outputs(str(tmp_path / 'c'), arrays)['harmonic']['rows'] == 'all'
+
+
+def test_plain_dry_run_line_and_dump():
+  """The plain command line end to end (dry: no device): one JSON line, exactly K timed steps in one region, outputs written."""
+  import tempfile
+  import numpy as np
+  with tempfile.TemporaryDirectory() as d:
+    r = _run_bench('--dry-run', '--steps', '5', '--warmup', '2', '--batch', '2', '--n-frames', '10', '--n-samples', '640',
+                   '--dump-outputs', d)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(out) == 1
+    line = json.loads(out[0])
+    assert line['steps'] == 5 and line['timing']['repeats'] == 1 and line['ms_per_step'] > 0 and 'cpu_baseline' not in line
+    assert sorted(os.listdir(d)) == ['filtered_noise.npy', 'harmonic.npy']
+    assert np.load(os.path.join(d, 'harmonic.npy')).dtype == np.float32
 
 
 def test_cpu_baseline_leg_runs_concurrent_workers_and_falls_back(monkeypatch):
@@ -392,7 +492,7 @@ def test_gpus_2_without_a_launcher_starts_its_own_ranks():
   step is a sleep) is the plumbing-test mode: what is checked is the launch, the rank logic, the barriers, the
   max-over-ranks reduction, the all-gather and the shape of the line - no number in it is a measurement."""
   r = _run_bench('--gpus', '2', '--dry-run', '--steps', '5', '--warmup', '2', '--batch', '2', '--n-frames', '10',
-                 '--n-samples', '640', '--allgather', '--no-cpu-baseline', '--north-star-batch', '4')
+                 '--n-samples', '640', '--allgather', '--no-cpu-baseline', '--north-star-batch', '4', '--full')
   assert r.returncode == 0, r.stderr[-2000:]
   out = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
   assert len(out) == 1
@@ -407,7 +507,7 @@ def test_default_shape_carries_configs_1_and_configs_4_two_ranks():
   """The default (north-star) shape on two ranks, dry: the line carries `configs_1` (BASELINE configs[1], batch 32) and
   `configs_4` (configs[4] per GPU: 48 kHz, 200 harmonics, 10 s clips, batch 32 - the 129 .. 200-harmonic instances of the
   Harmonic kernel) with the headline's definitions; every rank walks the same collectives through both blocks."""
-  r = _run_bench('--gpus', '2', '--dry-run', '--steps', '4', '--warmup', '1', '--no-cpu-baseline')
+  r = _run_bench('--gpus', '2', '--dry-run', '--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--full')
   assert r.returncode == 0, r.stderr[-2000:]
   line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
   assert line['config']['batch_per_gpu'] == 128 and line['configs_1']['batch_per_gpu'] == 32
@@ -423,7 +523,7 @@ def test_eight_ranks_dry_run_shards_of_the_sharded_configs_and_a_separate_gather
   configs[4] 256 -> 32, the headline 1024 -> 128: contiguous, disjoint, covering -, weak scaling, and --allgather reporting the
   gather's time in a field of its own, outside `ms_per_step`."""
   r = _run_bench('--gpus', '8', '--dry-run', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--allgather', '--repeats', '3',
-                 timeout=600)
+                 '--full', timeout=600)
   assert r.returncode == 0, r.stderr[-2000:]
   out = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
   assert len(out) == 1

@@ -14,7 +14,7 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | 
 echo "== bench, as the driver runs it (--steps 20 --warmup 5)"
 timeout 600 python bench.py --steps 20 --warmup 5 2>$OUT/bench_driver.err | tail -1 > $OUT/bench_driver_like.json; cut -c1-300 $OUT/bench_driver_like.json
 echo "== bench (defaults: 1000 steps)"
-timeout 600 python bench.py --no-cpu-baseline --also-other-mode 2>$OUT/bench_1000.err | tail -1 > $OUT/bench_1000.json
+timeout 600 python bench.py --no-cpu-baseline --also-other-mode --full 2>$OUT/bench_1000.err | tail -1 > $OUT/bench_1000.json
 python - <<PY
 import json
 d = json.load(open('$OUT/bench_1000.json'))
