@@ -472,7 +472,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 6 : 3)) void noise_fused65_kern
   const int own_lo = (blockIdx.x == 0) ? 0 : f_first + 2;
   const int own_hi = (z0 + kFnTile - 128) / p.fs + 2;          // f_first of the next tile + 2
   const float kLog10 = 2.302585092994046f;
-  // debug timeline (p.scale bit 30): ctl_out is reinterpreted as long long [blocks][8]
+  // clock stamps under p.scale bit 30 (ctl_out as long long [blocks][8]); no caller sets the bit, but without the branch the
+  // 8-wavefront build spills more and runs 47.0 -> 50.8 us at batch 128 (same-session A/B), so it stays
   const bool dbg_time = (p.scale & 0x40000000) != 0;
   long long* dbg = dbg_time ? reinterpret_cast<long long*>(ctl_out) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 : nullptr;
   int dbg_n = 0;
@@ -742,11 +743,6 @@ extern "C" int ddsp_filtered_noise_controls_f32(const float* magnitudes, float* 
   return check_launch();
 }
 
-static bool general_plain_env() {
-  static const bool v = [] { const char* e = getenv("DDSP_EXP_NOISE_GENERAL"); return e && e[0] == 'p'; }();
-  return v;
-}
-
 static int launch_ir(const float* mag, float* ctl_out, float* ir, int B, int F, int M,
                      int window_size, float bias, int scale, hipStream_t st) {
   const IrGeom g = ir_geom(M, window_size);
@@ -758,9 +754,8 @@ static int launch_ir(const float* mag, float* ctl_out, float* ir, int B, int F, 
     return check_launch();
   }
   const long rows = (long)B * F;
-  // any other filter: one matrix product with a constant matrix (filtered_noise_general.hip); DDSP_EXP_NOISE_GENERAL=plain
-  // keeps rounds 1-3's plain kernels (the A/B of tools/bench_generic.py)
-  if (!general_plain_env() && noise_ir_gemm_ok(M, window_size))
+  // any other filter: one matrix product with a constant matrix (filtered_noise_general.hip)
+  if (noise_ir_gemm_ok(M, window_size))
     return launch_noise_ir_gemm(mag, ctl_out, ir, rows, M, window_size, bias, scale, st);
   const size_t lds = (size_t)(g.L0 + M) * sizeof(float);
   if (lds > kMaxDynLds) return DDSP_ERR_UNSUPPORTED;
@@ -793,7 +788,7 @@ static bool fir_needs_noise_in_memory(int B, int F, int L, int N) {
   if (F <= 0 || N <= 0 || L <= 0) return false;
   const int frame_size = (N + F - 1) / F;
   if (L == 128 && frame_size == 64) return false;
-  if (!general_plain_env() && tv_fir_mfma_ok(B, B, F, L, N)) return false;
+  if (tv_fir_mfma_ok(B, B, F, L, N)) return false;
   size_t lds = 0;
   return fir_plain_tile(L, frame_size, lds) < 64;
 }
@@ -824,7 +819,7 @@ static int launch_fir(const float* x, const float* ir, float* out, int B, int Bi
     return check_launch();
   }
   // any other tap count and frame size: Toeplitz products on the matrix cores (filtered_noise_general.hip)
-  if (!general_plain_env() && tv_fir_mfma_ok(B, Bir, F, L, N))
+  if (tv_fir_mfma_ok(B, Bir, F, L, N))
     return launch_tv_fir_mfma(x, ir, out, B, Bir, F, L, N, p.start, seed, batch_offset, bits23, taps_bounded, st);
   // tile: as many outputs as keep x + taps under the LDS budget
   size_t lds = 0;
@@ -879,23 +874,18 @@ extern "C" int ddsp_filtered_noise_f32(const float* magnitudes, const float* noi
     return DDSP_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int scale = (flags & DDSP_NOISE_SCALE_EXP_SIGMOID) ? 1 : 0;
-  // bit 30 (the in-kernel timeline of tools/exp_noise_fir.py: the controls pointer then carries a stamp buffer) only
-  // under DDSP_NOISE_DEBUG_TIMELINE=1; any other unknown bit is an error, not a silent reinterpretation
-  static const bool dbg_allowed = getenv("DDSP_NOISE_DEBUG_TIMELINE") != nullptr;
-  const unsigned known = DDSP_NOISE_SCALE_EXP_SIGMOID | DDSP_NOISE_FIR_VECTOR_ALU | DDSP_NOISE_BITS_23 | (dbg_allowed ? 0x40000000u : 0u);
+  // an unknown bit is an error, not a silent reinterpretation
+  const unsigned known = DDSP_NOISE_SCALE_EXP_SIGMOID | DDSP_NOISE_FIR_VECTOR_ALU | DDSP_NOISE_BITS_23;
   if (flags & ~known) return DDSP_ERR_UNSUPPORTED;
   const int bits23 = (flags & DDSP_NOISE_BITS_23) ? 1 : 0;             // (generated noise only: supplied noise is what it is)
   {
     const IrGeom g = ir_geom(M, window_size);
     const int frame_size = (N + F - 1) / F;
     // default for the canonical filter: IR design AND the FIR on the matrix cores (filtered_noise_mfma.hip);
-    // DDSP_NOISE_FIR_VECTOR_ALU (or DDSP_EXP_NOISE_FIR=vector) keeps the FIR on the vector ALUs (noise_fused65_kernel)
-    static const bool fir_vector_env = [] { const char* e = getenv("DDSP_EXP_NOISE_FIR"); return e && e[0] == 'v'; }();
-    if (!(flags & DDSP_NOISE_FIR_VECTOR_ALU) && !fir_vector_env && B <= 65535 &&
-        noise_mfma65_ok(F, M, N, g.padding, noise, scale)) {
-      long long* dbg = (flags & 0x40000000u) ? reinterpret_cast<long long*>(ctl_magnitudes) : nullptr;   // debug timeline
-      return launch_noise_mfma65(magnitudes, noise, audio, dbg ? nullptr : ctl_magnitudes, B, F, N, (g.L - 1) / 2 - 1,
-                                 initial_bias, scale, seed, batch_offset, dbg, bits23, (float*)workspace, st);
+    // DDSP_NOISE_FIR_VECTOR_ALU keeps the FIR on the vector ALUs (noise_fused65_kernel)
+    if (!(flags & DDSP_NOISE_FIR_VECTOR_ALU) && B <= 65535 && noise_mfma65_ok(F, M, N, g.padding, noise, scale)) {
+      return launch_noise_mfma65(magnitudes, noise, audio, ctl_magnitudes, B, F, N, (g.L - 1) / 2 - 1,
+                                 initial_bias, scale, seed, batch_offset, bits23, (float*)workspace, st);
     }
     // (the vector-ALU kernel designs its taps on the matrix cores from magnitudes it splits as they come: squashed ones only)
     if (scale && M == 65 && g.padding == 0 && frame_size >= 64 && (frame_size % 16) == 0 && frame_size <= 4096 &&
@@ -904,7 +894,7 @@ extern "C" int ddsp_filtered_noise_f32(const float* magnitudes, const float* noi
       FusedNoiseArgs q;
       q.N = N; q.F = F; q.start = (g.L - 1) / 2 - 1; q.bias = initial_bias;
       q.fs = frame_size; q.inv_fs = 1.0f / (float)frame_size;
-      q.scale = scale | ((flags & 0x40000000u) ? 0x40000000 : 0);      // bit 30: debug timeline
+      q.scale = scale;
       q.k0 = (uint32_t)seed; q.k1 = (uint32_t)(seed >> 32); q.batch_offset = batch_offset; q.bits23 = bits23;
       const dim3 grid((unsigned)((N + q.start + kFnTile - 1) / kFnTile), (unsigned)B);
       hipEvent_t ev0, ev1;
@@ -912,9 +902,7 @@ extern "C" int ddsp_filtered_noise_f32(const float* magnitudes, const float* noi
       // 8-wavefront blocks (FIR tap range split in two) hide more latency once there is more than one
       // round of blocks (3 resident per CU); a single partial round next to the harmonic kernel on the
       // other stream does better with 4-wavefront blocks (measured: profiles/README.md)
-      static const int nw_env = [] { const char* e = getenv("DDSP_EXP_NOISE_WAVES"); return e ? atoi(e) : 0; }();
-      const int nw = nw_env ? nw_env : ((size_t)grid.x * grid.y > 768 ? 8 : 4);
-      if (nw == 8) {
+      if ((size_t)grid.x * grid.y > 768) {
         if (noise) hipExtLaunchKernelGGL((noise_fused65_kernel<false, 8>), grid, dim3(512), 0, st, ev0, ev1, 0,
                                          magnitudes, noise, ctl_magnitudes, audio, q);
         else hipExtLaunchKernelGGL((noise_fused65_kernel<true, 8>), grid, dim3(512), 0, st, ev0, ev1, 0,
@@ -929,9 +917,8 @@ extern "C" int ddsp_filtered_noise_f32(const float* magnitudes, const float* noi
     }
   }
   // any other filter of up to 128 bands and 256 taps, any frame size: one launch, the taps designed tile by tile in LDS
-  // (filtered_noise_general.hip); DDSP_EXP_NOISE_GENERAL=two keeps the design and the FIR apart (the larger filters' path)
-  static const bool two_env = [] { const char* e = getenv("DDSP_EXP_NOISE_GENERAL"); return e && e[0] == 't'; }();
-  if (!general_plain_env() && !two_env && filtered_noise_general_fused_ok(B, F, M, N, window_size))
+  // (filtered_noise_general.hip)
+  if (filtered_noise_general_fused_ok(B, F, M, N, window_size))
     return launch_filtered_noise_general_fused(magnitudes, noise, audio, ctl_magnitudes, B, F, M, N, window_size, initial_bias,
                                                scale, seed, batch_offset, bits23, st);
   float* ir = (float*)workspace;

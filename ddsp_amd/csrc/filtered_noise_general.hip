@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -126,9 +125,6 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
   const int S = 32 * KS + 4;
   const long block_row0 = (long)blockIdx.x * kGiRows;
   const int n_rows = (int)min((long)kGiRows, rows - block_row0);
-#ifdef DDSP_GI_NO_SCALE
-  scale = 0;
-#endif
   {
     const float* src = mag + block_row0 * M;
     float* ctl = ctl_out ? ctl_out + block_row0 * M : nullptr;
@@ -201,16 +197,11 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
 
   DDSP_GI_STASH(s_b);                       // (chunk 0 was fetched before the magnitudes: see the top of the kernel)
   __syncthreads();
-#ifdef DDSP_GI_NO_CHUNKS
-  NT = ah[0][0] == (_Float16)77.0f ? 1 : 0;
-#endif
 #pragma unroll 1
   for (int nt0 = 0, c = 0; nt0 < NT; nt0 += kNtg, ++c) {
     const int n_chunk = min(kNtg, NT - nt0);
     const uint4* buf = s_b + (c & 1) * kBuf;
-#ifndef DDSP_GI_NO_FETCH
     if (nt0 + kNtg < NT) DDSP_GI_FETCH(nt0 + kNtg);
-#endif
     // kG tap tiles at a time: 3 kG independent accumulation chains (a single tile's two chains of dependent MFMAs left
     // the matrix cores waiting for themselves: the loop was 11 of the kernel's 21 us at 100 bands, profiles/r05k)
     constexpr int kG = kNtg < 4 ? kNtg : 4;
@@ -229,19 +220,11 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
         for (int u = 0; u < kG; ++u) {
           // (tiles past the chunk's end multiply whatever the buffer holds: inside the buffer, never stored)
           const int t = t0 + u < kNtg ? t0 + u : kNtg - 1;
-#ifndef DDSP_GI_NO_LDSREAD
           const gf_f16x8 bh = __builtin_bit_cast(gf_f16x8, buf[((t * KS + ks) * 2 + 0) * 64 + lane]);
           const gf_f16x8 bl = __builtin_bit_cast(gf_f16x8, buf[((t * KS + ks) * 2 + 1) * 64 + lane]);
-#else
-          const gf_f16x8 bh = ah[(ks + t) % KS], bl = al[(ks + t) % KS];
-#endif
-#ifndef DDSP_GI_NO_MFMA
           acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], bh, acc[u], 0, 0, 0);
           acc_hl[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], bl, acc_hl[u], 0, 0, 0);
           acc_lh[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ks], bh, acc_lh[u], 0, 0, 0);
-#else
-          acc[u][0] += (float)bh[0] + (float)bl[1];
-#endif
         }
       }
       // D[row 4 g + r][column i]
@@ -253,11 +236,7 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
           for (int r = 0; r < 4; ++r) {
             const long rr = row0 + 4 * g + r;
             const float v = ldexpf(acc[u][r] + (acc_hl[u][r] + acc_lh[u][r]) * (1.0f / kGfLoScale), a_exp);
-#ifndef DDSP_GI_NO_STORE
             if (rr < rows) ir[rr * L + col] = v;
-#else
-            if (rr < rows && v == 1234.5f) ir[rr * L + col] = v;
-#endif
           }
         }
       }
@@ -630,9 +609,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       __syncthreads();
       h_exp = tile_exponent(2);
     }
-#ifdef DDSP_GF_NO_DESIGN_STAGE
-    if (p.M == 12345)
-#endif
     if (p.mag_vec) {
       const int m4 = p.M >> 2;
       for (int k = tid; k < rows_valid * m4; k += nthr) {
@@ -675,9 +651,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       for (int k = tid; k < (2 * p.tap_plane) >> 4; k += nthr) reinterpret_cast<uint4*>(s_taps)[k] = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
-#ifdef DDSP_GF_NO_DESIGN_MFMA
-    if (p.M == 12345)
-#endif
     {
       const int i16 = lane & 15, g = lane >> 4;
 #pragma unroll
@@ -723,21 +696,17 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
   }
 
   // ---- zero everything a stale value could be read from --------------------------------------------------------------
-  // (DDSP_GF_NO_*: parts of the kernel compiled out for tools/exp_noise_general.py's time accounting - wrong results)
-#ifndef DDSP_GF_NO_ZERO
   {
     const int n16 = (4 * p.out_len + (GEN ? 1 : 2) * p.x_part) >> 4;
     uint4* z = reinterpret_cast<uint4*>(smem);
     for (int k = tid; k < n16; k += nthr) z[k] = make_uint4(0u, 0u, 0u, 0u);
   }
-#endif
   __syncthreads();
   if constexpr (!GEN) x_exp = tile_exponent(0);
   if constexpr (KS == 0) h_exp = tile_exponent(1);
   const int o_exp = x_exp + h_exp;
 
   // ---- the taps of the tile's frames: fp32 rows from HBM, split, as groups of 8 ------------------------------------------
-#ifndef DDSP_GF_NO_TAPS
   if constexpr (KS == 0) {
     const float* irb = p.ir + (size_t)b * p.ir_batch_stride;
     const int gpr = 2 * (p.Q + 1);                           // groups per row, the zero groups included
@@ -773,7 +742,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       *reinterpret_cast<gf_f16x8*>(dst + p.tap_plane) = lo;
     }
   }
-#endif
 
   // ---- the noise: reversed inside its piece's slot, two copies one element apart ---------------------------------------
   // sample i of piece v (first sample s, frame position rem) sits at slot element j' = s mod 16 + (i - s), stored at
@@ -795,7 +763,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       *reinterpret_cast<_Float16*>(s_x + x_lo + p.x_o + 2 * (el + 1)) = lo;
     }
   };
-#ifndef DDSP_GF_NO_NOISE
   if constexpr (GEN) {
     for (int q = (i_lo >> 3) + tid; 8 * q < i_end; q += nthr) {
       const U4 r = noise_philox(U4{(uint32_t)q, (uint32_t)(p.batch_offset + b), 0u, 0u}, p.k0, p.k1);
@@ -821,7 +788,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
     const float* xb = p.x + (size_t)b * p.N;
     for (int i = i_lo + tid; i < i_end; i += nthr) place(i, xb[i]);
   }
-#endif
   __syncthreads();
 
   // ---- a wavefront's run of pieces -------------------------------------------------------------------------------------
@@ -836,7 +802,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
   int Z_run = 0;
   bool have = false;
   const int v_first = Vt0 + wave * p.R;
-#ifndef DDSP_GF_NO_MFMA
   if (wave < p.W) {
     // element 79 - (16 p + i - 8 (g & 1)) of the slot, p = 2 c + (g >> 1): its parity is that of 79 - i for every step
     const int x_copy = (i16 & 1) ? 0 : p.x_o + 2;           // even element -> copy E; odd -> copy O, one element further
@@ -881,7 +846,6 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       }
     }
   }
-#endif
   // ---- the runs into the output buffer: a run OWNS the outputs up to where the next run's begin and writes them; what
   // it adds to the next run's (its taps reach that far, and no further: gf_plan) it adds once those are written, behind a
   // barrier.  No output is touched by two wavefronts at a time and every sum has one order.  (ds_add_f32 here was 33 of
@@ -928,11 +892,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
     float* ob = p.out + (size_t)b * p.N;
     const int k_lo = max(max(z_lo, p.start) - Z_t0, 0);
     const int k_hi = min(min(z_hi, p.N + p.start) - Z_t0, p.out_len);
-#ifndef DDSP_GF_NO_STORE
     for (int k = k_lo + tid; k < k_hi; k += nthr) ob[Z_t0 + k - p.start] = s_out[k];
-#else
-    if (k_lo + tid == k_hi + 12345) ob[0] = s_out[tid];
-#endif
   }
 }
 
@@ -959,14 +919,9 @@ static GfPlan gf_plan(int F, int L, int N, bool gen, int design_ks = 0) {
     int r_min = 1;
     while (r_min <= r_max && (long)(r_min / npf) * fs < L - 1 + 15) ++r_min;
     if (r_min > r_max) continue;
-    // DDSP_EXP_GF_PLAN=W,R pins the cut (tools/exp_noise_general.py's sweep)
-    static const char* plan_env = getenv("DDSP_EXP_GF_PLAN");
-    int w_env = 0, r_env = 0;
-    if (plan_env && sscanf(plan_env, "%d,%d", &w_env, &r_env) != 2) w_env = r_env = 0;
-    for (int R : {r_max, (r_max + r_min) / 2, r_min, r_env}) {
-      if (R < r_min || R > r_max || (r_env && R != r_env)) continue;
+    for (int R : {r_max, (r_max + r_min) / 2, r_min}) {
+      if (R < r_min || R > r_max) continue;
       for (int W : {8, 4, 2}) {
-        if (w_env && W != w_env) continue;
         if (design_ks && W != 8) continue;                      // (a tap tile per wavefront and round: eight wavefronts)
         const int WR = W * R;
         const int fresh = WR - hist;
@@ -1334,8 +1289,7 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
 }
 
 bool noise_bwd_mfma_ok(int B, int F, int M, int N, int window_size) {
-  static const bool off = [] { const char* e = getenv("DDSP_EXP_NOISE_BWD"); return e && e[0] == 'p'; }();      // "plain": the two kernels of rounds 1-3
-  if (off || B <= 0 || B > 65535 || F <= 0 || N <= 0 || M != 65) return false;
+  if (B <= 0 || B > 65535 || F <= 0 || N <= 0 || M != 65) return false;
   const IrGeom g = ir_geom(M, window_size);
   if (g.padding != 0) return false;
   const int fs = (N + F - 1) / F;

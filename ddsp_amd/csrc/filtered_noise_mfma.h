@@ -15,6 +15,6 @@ bool noise_mfma65_ok(int F, int M, int N, int padding, const void* noise, int sc
 // row_scratch: B floats of workspace for the rows' max |noise| when noise is supplied (it is normalised before the fp16 split)
 int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audio, float* ctl_magnitudes, int B, int F,
                         int N, int start, float initial_bias, int scale, uint64_t seed, uint64_t batch_offset,
-                        long long* dbg, int bits23, float* row_scratch, hipStream_t st);
+                        int bits23, float* row_scratch, hipStream_t st);
 
 }  // namespace ddsp

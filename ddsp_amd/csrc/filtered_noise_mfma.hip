@@ -52,13 +52,10 @@ namespace ddsp {
 // Block size.  8 wavefronts (4 producers + 4 FIR) on tiles of 30 output frames, TWO blocks per CU: each block has its own
 // barrier, so one block's wait at it is the other block's time (13.7 / 39.1 us at batch 32 / 128).  The two blocks of a
 // CU do not advance together - the arbiter prefers the older block's wavefronts: its ticks take 2.8 us, the younger
-// block's 4.5-6 us until the older one is done (DDSP_MF_DBG_BLOCK picks the block the timeline shows).  16 wavefronts on tiles of
-// 62 frames, one block per CU (-DDDSP_MF_WAVES=16): 3 % less history to recompute, but every tick ends with sixteen
+// block's 4.5-6 us until the older one is done.  16 wavefronts on tiles of
+// 62 frames, one block per CU: 3 % less history to recompute, but every tick ends with sixteen
 // wavefronts waiting for the slowest (15.2 / 40.7 us; profiles/r02_final2_noise_mfma_two_blocks_per_cu.txt).
-#ifndef DDSP_MF_WAVES
-#define DDSP_MF_WAVES 8
-#endif
-constexpr int kMfWaves = DDSP_MF_WAVES;
+constexpr int kMfWaves = 8;
 constexpr int kMfPW = kMfWaves / 2;            // producer wavefronts = FIR wavefronts
 constexpr int kMfRows = 8 * kMfPW;             // staged frames: 2 of history + the tile's (a producer row group = 16 rows
                                                // x 2 tap tiles; an FIR wavefront = 4 pairs = 8 frames): 32
@@ -111,9 +108,6 @@ struct MfArgs {
   int tiles_per_row, n_tiles;       // tiles of 62 frames per batch row; B * tiles_per_row
   FastDiv whole_per_row, fs_div;    // max(tiles_per_row - 1, 1); fs
   int n_whole;                      // B * (tiles_per_row - 1): the tiles before the rows' last ones
-  int dbg_block;                    // the block whose times are stamped (DDSP_MF_DBG_BLOCK, default 0)
-  int dbg_wave;                     // the FIR wavefront (8 .. 15) whose times are stamped; the producer is dbg_wave - 8
-  long long* dbg;                   // block 0's per-tick stamps [16 ticks][3 roles][begin, end] (tools/exp_noise_fir.py), or null
   // The hi / lo instances (GEN_NOISE = false) serve two callers.  Noise the caller SUPPLIES comes at any scale: x_absmax[row] =
   // max |noise[row]| (row_absmax_kernel, a launch ahead of this one) gives the power of two that brings the row to [1/2, 1)
   // before the fp16 split and the outputs back (the FIR is linear in the noise).  And DDSP_NOISE_BITS_23: x == null,
@@ -291,8 +285,6 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mi = lane & 15, mg = lane >> 4;            // MFMA fragment coordinates
   const int n_my = (p.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;     // tiles of this block
-  long long* dbg = (p.dbg && (int)blockIdx.x == p.dbg_block) ? p.dbg : nullptr;                              // block 0: [tick][role][2]
-#define DDSP_MF_STAMP(tick, role, i) do { if (dbg && lane == 0 && (tick) + 1 < 16) dbg[(((tick) + 1) * 3 + (role)) * 2 + (i)] = wall_clock64(); } while (0)
   // tile T -> (batch row, tile tx of the row): first output z0 = 3968 tx (a multiple of 64); tap rows: frames f_first ..
   // f_first + 63 (frames of the inputs x[z0-128 ..]); negative for the first tile.  The rows' LAST tiles come last in the
   // order (T >= n_whole): they are mostly beyond the end of the row (a 4 s clip is 16.1 tiles) and cost a fraction of a
@@ -434,7 +426,6 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       if constexpr (HANDOFF) fetch_rows(1);          // (the block's second tile: its first is the designers' own)
 #pragma unroll 1
       for (int tick = -1; tick < n_my; ++tick) {
-        if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 0, 0);
         if constexpr (HANDOFF) {
           // the magnitudes of tile tick + 2, for the designers' next tick
           if (tick + 2 < n_my) {
@@ -453,7 +444,6 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           fetch_rows(tick + 3);                      // used a tick from now
         }
         make_noise(tick);
-        if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 0, 1);
         __syncthreads();
       }
     } else {
@@ -515,11 +505,9 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       // noise is supplied) or taken from the noise makers' handoff
       auto designer_tick = [&](int tick, auto scale_here_tag) {
         constexpr bool SCALE_HERE = decltype(scale_here_tag)::value;
-        if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 0, 0);
         if (tick + 1 < n_my) {
           const int T = (int)blockIdx.x + (tick + 1) * (int)gridDim.x;
           unsigned char* const s_taps = s_taps_all[(tick + 1) & 1];
-          if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 1, 0);
           if constexpr (SCALE_HERE) {
             mf_f16x8 be_hi, be_lo, bo_hi, bo_lo;
             float m_last = 0.0f, t32 = 0.0f;
@@ -534,13 +522,11 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
                           h.last[rrow], h.tap32[rrow]);
             }
           }
-          if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 1, 1);
         }
         // supplied noise: the magnitudes of tile tick + 2, used a tick from now - fetched at the END of the tick, into the
         // registers this tick's magnitudes have just left (past the block's last tile: the last one again)
         if (!HANDOFF) fetch_rows(tick + 2);
         if constexpr (HANDOFF) make_noise(tick);
-        if (wave == p.dbg_wave - 8) DDSP_MF_STAMP(tick, 0, 1);
         __syncthreads();
       };
       designer_tick(-1, std::true_type{});
@@ -597,7 +583,6 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     };
 #pragma unroll 1
     for (int tick = -1; tick < n_my; ++tick) {
-      if (wave == p.dbg_wave - 8 + kMfPW) DDSP_MF_STAMP(tick, 2, 0);
       if (tick >= 1) flush_kept((tick - 1) & 1);
       if (tick < 0) {
         // nothing to filter yet: the noise of the block's first tile, while the producers design its taps
@@ -751,12 +736,10 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       } else {
         kept_ot = nullptr;
       }
-      if (wave == p.dbg_wave - 8 + kMfPW) DDSP_MF_STAMP(tick, 2, 1);
       __syncthreads();
     }
     flush_kept((n_my - 1) & 1);                // the last tile's boundaries (nothing writes s_carry any more)
   }
-#undef DDSP_MF_STAMP
 #undef DDSP_MF_TILE
 }
 
@@ -786,7 +769,7 @@ __global__ __launch_bounds__(1024) void row_absmax_kernel(const float* __restric
 
 int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audio, float* ctl_magnitudes, int B, int F,
                         int N, int start, float initial_bias, int scale, uint64_t seed, uint64_t batch_offset,
-                        long long* dbg, int bits23, float* row_scratch /* B floats */, hipStream_t st) {
+                        int bits23, float* row_scratch /* B floats */, hipStream_t st) {
   MfArgs q;
   q.x_absmax = nullptr; q.bits23 = bits23;
   if (noise) {
@@ -798,11 +781,6 @@ int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audi
   q.N = N; q.F = F; q.start = start; q.bias = initial_bias; q.scale = scale;
   q.fs = (N + F - 1) / F; q.inv_fs = 1.0f / (float)q.fs;
   q.k0 = (uint32_t)seed; q.k1 = (uint32_t)(seed >> 32); q.batch_offset = batch_offset;
-  q.dbg = dbg;
-  static const int dbg_wave = [] { const char* e = getenv("DDSP_MF_DBG_WAVE"); const int v = e ? atoi(e) : 8; return v >= 8 && v < 8 + kMfPW ? v : 8; }();
-  q.dbg_wave = dbg_wave;
-  static const int dbg_block = [] { const char* e = getenv("DDSP_MF_DBG_BLOCK"); return e ? atoi(e) : 0; }();
-  q.dbg_block = dbg_block;
   q.tiles_per_row = (N + start + kMfTile - 1) / kMfTile;
   q.n_tiles = B * q.tiles_per_row;
   q.whole_per_row = make_fastdiv((uint32_t)(q.tiles_per_row > 1 ? q.tiles_per_row - 1 : 1));

@@ -535,13 +535,6 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
   __shared__ UnitTables<FPB> t;
   float* __restrict__ ctl_amp = STD ? nullptr : ctl_amp_arg;
   float* __restrict__ ctl_hd = STD ? nullptr : ctl_hd_arg;
-  // debug timeline (flag 0x02000000, generic variant only): ctl_amp is reinterpreted as long long [gridDim.x][16]
-  const bool dbg_time = !STD && (p.flags & 0x02000000u) != 0;
-  long long* dbg = dbg_time ? reinterpret_cast<long long*>(ctl_amp_arg) + (size_t)blockIdx.x * 16 : nullptr;
-  int dbg_n = 0;
-#define DDSP_STAMP() do { if (!STD && dbg_time && threadIdx.x == 0 && dbg_n < 16) dbg[dbg_n++] = wall_clock64(); } while (0)
-  if (dbg_time) ctl_amp = nullptr;
-  DDSP_STAMP();
   constexpr int RPW = 64 / LPR;                          // matrix rows per wavefront per pass
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -604,7 +597,6 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
       if (live && r <= nfr)
         *reinterpret_cast<float4*>(&wsu[r * Kp + 4 * kq]) = make_float4(a * h.x, a * h.y, a * h.z, a * h.w);
     }
-    DDSP_STAMP();                                      // 1: rows issued
     // ---------------- phase A, phase wave: fp64 prefix and everything that is per frame ------------
     // Frame j carries f[t] = f_j + (f_{j+1}-f_j) r/hop (legacy bilinear resize of f0), whose sum over
     // the frame is hop*f_j + (f_{j+1}-f_j)(hop-1)/2; summed over j < J this telescopes to
@@ -657,11 +649,9 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
         t.kN[lane] = kN;
       }
     }
-    DDSP_STAMP();                                      // 2: tables issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's rows have reached L2
     __syncthreads();
     if (STD || !(p.flags & 0x08000000u)) __builtin_amdgcn_s_dcache_inv();   // drop stale scalar-cache lines of the slot
-    DDSP_STAMP();                                      // 3: slot + tables visible
 
     // ---------------- phase B: tiles of 64 samples ---------------------------------------------
     const int hop = p.hop;
@@ -737,7 +727,6 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
       const float w_cur = 1.0f - w_next;
       audio[(size_t)(row0 + q) * hop + r] = w_cur * acc0 + w_next * acc1;      // N == F * hop
     }
-    DDSP_STAMP();                                      // 4: tiles done
     if (p.n_units <= (int)gridDim.x) return;           // one unit per block: nothing to pull or reset
     if (tid == 0) t.next_unit = xcls + 8 * (first_pull + (int)atomicAdd(counter, 1u));
     __syncthreads();              // also: the slot and the LDS tables are rewritten by the next unit
@@ -750,7 +739,6 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
       __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#undef DDSP_STAMP
 }
 
 }  // namespace ddsp
@@ -796,12 +784,7 @@ static int launch_fused(const float* amps, const float* hd, const float* f0, flo
   p.half_hm1 = ((double)p.hop - 1.0) * 0.5;
   p.nyq_lo = p.nyquist * (1.0f - 4e-6f);
   p.nyq_hi = p.nyquist * (1.0f + 4e-6f);
-  static const int max_blocks = [] {
-    const char* e = getenv("DDSP_EXP_HARM_BLOCKS");
-    const int v = e ? atoi(e) : kFusedMaxBlocks;
-    return v > 0 && v <= kFusedMaxBlocks ? v : kFusedMaxBlocks;
-  }();
-  const dim3 grid((unsigned)(p.n_units < max_blocks ? p.n_units : max_blocks)), block(256);
+  const dim3 grid((unsigned)(p.n_units < kFusedMaxBlocks ? p.n_units : kFusedMaxBlocks)), block(256);
   static std::atomic<unsigned> ticket{0};
   p.sched_set = (int)(ticket.fetch_add(1u) % (unsigned)kSchedSets);
   // A set may only be handed out again when the launch that had it last is done: launches on ONE stream are, by stream
@@ -1144,16 +1127,10 @@ __global__ __launch_bounds__(64 * NW) void harm_bwd_pq_kernel(const float* __res
   }
 }
 
-#ifndef DDSP_CHAIN_ROWS
-#define DDSP_CHAIN_ROWS 1
-#endif
-constexpr int kChainRows = DDSP_CHAIN_ROWS;
-// wavefronts (= rows) per block (-DDDSP_CHAIN_WAVES): 19.2 / 19.2 / 19.7 us at batch 32 and 57 / 60 / 63 at batch 128 for 4 / 8 / 16
+constexpr int kChainRows = 1;
+// wavefronts (= rows) per block: 19.2 / 19.2 / 19.7 us at batch 32 and 57 / 60 / 63 at batch 128 for 4 / 8 / 16
 // (round 5, profiles/r05o: not the rate blocks are launched at either): four it stays
-#ifndef DDSP_CHAIN_WAVES
-#define DDSP_CHAIN_WAVES 4
-#endif
-constexpr int kChainWaves = DDSP_CHAIN_WAVES;
+constexpr int kChainWaves = 4;
 template <int NCHUNK>   // ceil(K/64) <= NCHUNK
 __global__ __launch_bounds__(64 * kChainWaves) void harm_bwd_chain_kernel(const float* __restrict__ amplitudes,
                                                              const float* __restrict__ hd,
@@ -1165,7 +1142,7 @@ __global__ __launch_bounds__(64 * kChainWaves) void harm_bwd_chain_kernel(const 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // dL/da[j] = P[j] + Q[j-1]; the last frame also receives Q[F-1] (row F repeats row F-1)
   const int F = p.F;
-  // kChainRows rows per wavefront (-DDDSP_CHAIN_ROWS): measured 20.1 / 21.5 / 22.4 us for 1 / 2 / 4 rows at batch 32 (r05y) - the
+  // kChainRows rows per wavefront: measured 20.1 / 21.5 / 22.4 us for 1 / 2 / 4 rows at batch 32 (r05y) - the
   // kernel is not waiting for its loads; one row it stays
 #pragma unroll
   for (int u = 0; u < kChainRows; ++u) {
@@ -1238,9 +1215,7 @@ extern "C" int ddsp_harmonic_backward_f32(const float* amplitudes, const float* 
     // up to 128 harmonics: spread the weighted gradient onto the table grid, one product with the transposed sine matrix
     // (harmonic_bwd_table.hip) instead of a sine per sample and harmonic
     ProfileScope prof(kHarmBwdTable, st);
-    rc = launch_harm_bwd_table(f0_hz, theta0, grad_audio, pq, q_offset, B, F, K, N, sample_rate, p.amp_linear, st, amplitudes, hd,
-                               grad_amplitudes, grad_hd, flags, inputs_are_controls);
-    if (rc == 1) return check_launch();            // the chain rule ran in the same launch
+    rc = launch_harm_bwd_table(f0_hz, theta0, grad_audio, pq, q_offset, B, F, K, N, sample_rate, p.amp_linear, st);
     if (rc != DDSP_OK) return rc;
   } else {
     ProfileScope prof(kHarmBwdPq, st);

@@ -26,7 +26,7 @@
 //      quarter range: Go / Ge for odd / even harmonics, split into fp16 hi / lo B-fragment planes, 16 columns = 8 frames x {P, Q}.
 //   3. Wavefront w = (parity w & 1, harmonic tile w >> 1): 4 k-steps x 3 v_mfma_f32_16x16x32_f16 against its constant
 //      A-fragments (32 registers, loaded once per block: blocks are persistent), the results through LDS to whole rows of
-//      the P / Q workspace (or, DDSP_EXP_HARM_BWD=fused, into the chain rule of harmonic_bwd_chain.h without leaving LDS).
+//      the P / Q workspace.
 // Harmonics that cross Nyquist inside a frame ([kA, kN): the audio-rate mask of oscillator_bank, core.py:942-944) get the masked
 // samples' contribution subtracted again, evaluated directly (one sine per sample and crossing harmonic, a wave reduction);
 // harmonics >= kN are zero.  Frames the scheme does not cover (f0 < sr / 512: positions closer than one entry; f0 <= 0 or NaN;
@@ -43,13 +43,10 @@
 #include "harm_table_frags.h"
 #include "profile.h"
 #include "harmonic_bwd_table.h"
-#include "harmonic_bwd_chain.h"
 
 namespace ddsp {
 
-#ifndef DDSP_BT_MIN_WAVES
-#define DDSP_BT_MIN_WAVES 4
-#endif
+constexpr int kBtMinWaves = 4;
 constexpr int kBtT = 512;
 constexpr int kBtFrames = 8;                 // frames = wavefronts per block
 constexpr int kBtCol = 136;                  // halves per column of a folded plane: 128 + 8 (columns 68 dwords apart)
@@ -71,10 +68,6 @@ struct BtArgs {
   long rows;                   // B F
   float sample_rate, nyquist;
   int amp_linear;
-  // CHAIN: the frame-rate chain rule in the same launch (harmonic_bwd_chain.h); P and Q never leave LDS
-  const float* amplitudes; const float* hd; float* grad_amp; float* grad_hd;
-  BwdArgs chain;
-  long long* dbg;              // per-phase clock stamps of block 0 (tools/exp_bwd_timeline.py: DDSP_EXP_BT_TIMELINE = a device pointer), or null
 };
 
 template <int W> struct BtPoly;
@@ -103,18 +96,13 @@ __device__ __forceinline__ void bt_split(float v, _Float16& hi, _Float16& lo) {
   lo = (_Float16)((v - (float)hi) * kBtLoScale);
 }
 
-// CHAIN: groups advance by SEVEN frames - wavefront 0's frame is the one before the group's (its Q is what the group's first
-// frame adds to its P), computed here once more rather than fetched from another block
-template <int W, bool CHAIN>
-__global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES) void harm_bwd_table_kernel(BtArgs p) {
+template <int W>
+__global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void harm_bwd_table_kernel(BtArgs p) {
   // 129 .. 200 harmonics (W = 10: BASELINE configs[4]'s shapes): SIXTEEN wavefronts - eight of them spread a frame each as below,
   // fourteen take a (parity, harmonic tile) of the product: seven tiles of 16 per parity, each with its 32 registers of fragments
   constexpr int kMt = W == 10 ? 7 : 4, kMtAlloc = W == 10 ? 8 : 4;
   constexpr int kNch = W == 10 ? 4 : 2;                         // harmonics per lane where lanes = harmonics
   constexpr int kOutStride = W == 10 ? 212 : 132;
-  constexpr int kStep = CHAIN ? kBtFrames - 1 : kBtFrames, kBack = CHAIN ? 1 : 0;
-  int dbg_iter = 0;
-#define DDSP_BT_STAMP(pt) do { if (p.dbg != nullptr && blockIdx.x == 0 && lane == 0 && dbg_iter < 16) p.dbg[(dbg_iter * 8 + wave) * 8 + (pt)] = (long long)__builtin_readcyclecounter(); } while (0)
   __shared__ __attribute__((aligned(16))) float2 s_g[kBtFrames][kBtT];            // 32 KB
   __shared__ __attribute__((aligned(16))) _Float16 s_b[2][2][16][kBtCol];         // [hi / lo][parity][column][n]: 17 KB
   __shared__ float s_corr[kBtFrames][2][kBtMaxCross];
@@ -138,14 +126,14 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
   // the first tile's gradient samples of a group are requested a group ahead (a group is a chain of dependent steps with two
   // block barriers in it; the HBM latency at its head was a fifth of it)
   auto first_tile = [&](long r0) -> float {
-    const long rw = r0 + wave - kBack;
+    const long rw = r0 + wave;
     if (!has_frame || rw < 0 || rw >= p.rows || lane >= p.hop) return 0.0f;
     return p.g[(size_t)rw * p.hop + lane];           // row (b, j): sample b N + j hop + lane = row hop + lane
   };
   // ... and so are the frame's two f0 values and its phase: everything a group's first instruction depends on
   struct Head { float fj, fj1; double th0; };
   auto frame_head = [&](long r0) -> Head {
-    const long rw = r0 + wave - kBack;
+    const long rw = r0 + wave;
     Head h{0.0f, 0.0f, 0.0};
     if (has_frame && rw >= 0 && rw < p.rows) {
       const long jj = rw % p.F;
@@ -155,20 +143,16 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
     }
     return h;
   };
-  float g_next = first_tile((long)blockIdx.x * kStep);
-  Head h_next = frame_head((long)blockIdx.x * kStep);
+  float g_next = first_tile((long)blockIdx.x * kBtFrames);
+  Head h_next = frame_head((long)blockIdx.x * kBtFrames);
 #pragma unroll 1
-  for (long row0 = (long)blockIdx.x * kStep; row0 < p.rows; row0 += (long)gridDim.x * kStep) {
-  const long row = row0 + wave - kBack;
+  for (long row0 = (long)blockIdx.x * kBtFrames; row0 < p.rows; row0 += (long)gridDim.x * kBtFrames) {
+  const long row = row0 + wave;
   const bool row_ok = has_frame && row >= 0 && row < p.rows;
   const float g_first = g_next;
   const Head head = h_next;
-  g_next = first_tile(row0 + (long)gridDim.x * kStep);
-  h_next = frame_head(row0 + (long)gridDim.x * kStep);
-  float dP[kNch], dQ[kNch];                                      // the plain sum's results (CHAIN: into LDS behind the barrier)
-#pragma unroll
-  for (int c = 0; c < kNch; ++c) { dP[c] = 0.0f; dQ[c] = 0.0f; }
-  DDSP_BT_STAMP(0);
+  g_next = first_tile(row0 + (long)gridDim.x * kBtFrames);
+  h_next = frame_head(row0 + (long)gridDim.x * kBtFrames);
 
   // ---- 1. spreading -----------------------------------------------------------------------------------------------------------
   if (has_frame) {
@@ -213,9 +197,6 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
       c_cur = (1.0f - w_next) * gv;
       c_next = w_next * gv;
     };
-#ifdef DDSP_BT_NO_SPREAD
-    if (p.K == 12345)
-#endif
     if (!direct) {
       if (lane < 2 * kBtMaxCross) s_corr[wave][lane >> 3][lane & 7] = 0.0f;
 #pragma unroll 1
@@ -242,9 +223,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
         // less than T over the tile, whatever revolution they fall in.  At 70 Hz a tile spans 143 entries, 28 % of the tiles wrap,
         // and with eight frames per group nearly every group waited for a wavefront that ran the W read-modify-writes twice
         // (round 6).
-#ifndef DDSP_EXP_BT_TWO_TURNS         // (the A/B switch of tools/exp_bwd.py)
         if (__builtin_amdgcn_readlane(i_abs, last_live) - __builtin_amdgcn_readfirstlane(i_abs) < kBtT) { rev = 0; rev_last = 0; }
-#endif
         const float zz = z * z;
         float w_lo[W / 2], w_hi[W / 2];
 #pragma unroll
@@ -259,7 +238,6 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
         }
 #pragma unroll 1
         for (int rv = 0; rv <= rev_last; ++rv) {
-#ifndef DDSP_BT_NO_RMW
           if (rev == rv && live) {
             // W read-modify-writes, one tap number at a time: within a tap number the lanes of a revolution hit distinct entries
 #pragma unroll
@@ -274,7 +252,6 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
               *e = v;
             }
           }
-#endif
         }
         // harmonics that cross Nyquist in this frame: what their masked samples put into G comes out again
         if (kN > kA) {
@@ -322,23 +299,16 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
           }
         }
       }
-      if constexpr (CHAIN) {
+      const size_t at = (size_t)row * p.K;
 #pragma unroll
-        for (int c = 0; c < kNch; ++c) { dP[c] = Pd[c]; dQ[c] = Qd[c]; }
-      } else {
-        const size_t at = (size_t)row * p.K;
-#pragma unroll
-        for (int c = 0; c < kNch; ++c)
-          if (lane + 64 * c < p.K) { p.pq[at + lane + 64 * c] = Pd[c]; p.pq[p.q_offset + at + lane + 64 * c] = Qd[c]; }
-      }
+      for (int c = 0; c < kNch; ++c)
+        if (lane + 64 * c < p.K) { p.pq[at + lane + 64 * c] = Pd[c]; p.pq[p.q_offset + at + lane + 64 * c] = Qd[c]; }
     }
   }
   if (has_frame && lane == 0) { s_k[wave][0] = kA; s_k[wave][1] = kN; s_k[wave][2] = direct; }
   __builtin_amdgcn_wave_barrier();
-  DDSP_BT_STAMP(1);
 
   // ---- 2. folding onto the quarter range, split, B-fragment planes: columns 2 w (P) and 2 w + 1 (Q) -----------------------------
-#ifndef DDSP_BT_NO_FOLD
   if (has_frame) {
     const float2* G = &s_g[wave][0];
     float v[2][2][2];                                                           // [half][parity: odd k, even k][P, Q]
@@ -370,15 +340,9 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
         }
     }
   }
-#endif
-  DDSP_BT_STAMP(2);
   __syncthreads();
-  DDSP_BT_STAMP(3);
 
   // ---- 3. D[harmonic][column] = sum_n A[harmonic][n] G_folded[n][column] ------------------------------------------------------------
-#ifdef DDSP_BT_NO_P3
-  if (p.K == 12345)
-#endif
   if (has_task) {
     const int i16 = lane & 15, g4 = lane >> 4;
     bt_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
@@ -406,34 +370,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
       }
     }
   }
-  DDSP_BT_STAMP(4);
-  if constexpr (CHAIN) {
-    if (row_ok && s_k[wave][2]) {          // (s_out's readers of the previous group are behind the barrier above)
-#pragma unroll
-      for (int c = 0; c < kNch; ++c) { s_out[2 * wave][lane + 64 * c] = dP[c]; s_out[2 * wave + 1][lane + 64 * c] = dQ[c]; }
-    }
-  }
   __syncthreads();
-  DDSP_BT_STAMP(5);
-  if constexpr (CHAIN) {
-    // the chain rule of frame `row` (wavefronts 1 .. 7): dL/da = P[row] + Q[row - 1] (wavefront w - 1's, same batch row) (+ Q[row]
-    // for the held last frame)
-    if (wave >= 1 && row_ok) {
-      const int j = (int)(row % p.F);
-      const float* P = s_out[2 * wave];
-      const float* Qp = s_out[2 * wave - 1];
-      const float* Qo = s_out[2 * wave + 1];
-      harm_chain_row<kNch>(lane, row, j, p.amplitudes, p.hd, p.f0, p.grad_amp, p.grad_hd, p.chain, [&](int k) {
-        float gsum = P[k];
-        if (j > 0) gsum += Qp[k];
-        if (j == p.F - 1) gsum += Qo[k];
-        return gsum;
-      }, [](float v) { return v; });
-    }
-  } else
-#ifdef DDSP_BT_NO_STORE
-  if (p.K == 12345)
-#endif
   if (row_ok && !s_k[wave][2]) {
     // wavefront w writes its own frame's two rows
 #pragma unroll
@@ -444,10 +381,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, DDSP_BT_MIN_WAVES)
         if (lane + 64 * c < p.K) dst[lane + 64 * c] = s_out[2 * wave + q][lane + 64 * c];
     }
   }
-  DDSP_BT_STAMP(6);
-  ++dbg_iter;
   }    // the block's next group of frames
-#undef DDSP_BT_STAMP
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -496,19 +430,14 @@ static const bt_u32x4* bt_fragments(int W) {
 int harm_bwd_table_prepare(int K) { return bt_fragments(K <= 100 ? 6 : (K <= 128 ? 8 : 10)) ? 0 : 1; }
 
 bool harm_bwd_table_ok(int F, int K, int N) {
-  static const bool off = [] { const char* e = getenv("DDSP_EXP_HARM_BWD"); return e && e[0] == 'p'; }();   // "plain": the sums
   const int hop = F > 0 ? N / F : 0;
-  return !off && K >= 1 && K <= 200 && hop >= 1 && (long)F * hop == N && hop <= 4096;
+  return K >= 1 && K <= 200 && hop >= 1 && (long)F * hop == N && hop <= 4096;
 }
 
 int launch_harm_bwd_table(const float* f0_hz, const double* theta0, const float* grad_audio, float* pq, size_t q_offset, int B,
-                          int F, int K, int N, int sample_rate, int amp_linear, hipStream_t st, const float* amplitudes,
-                          const float* hd, float* grad_amp, float* grad_hd, unsigned flags, int inputs_are_controls) {
-  // The chain rule in the same launch (CHAIN) is correct and is NOT the default: it puts seven more dependent steps into every
-  // group's chain and recomputes a frame in eight - 60.1 us against 41.6 + 21.2 in two launches at batch 32, 215 against 135 + 66
-  // at batch 128 (profiles/r05_harm_bwd_table.txt).  DDSP_EXP_HARM_BWD=fused runs it.
-  static const bool fused = [] { const char* e = getenv("DDSP_EXP_HARM_BWD"); return e && e[0] == 'f'; }();
-  const bool chain = amplitudes != nullptr && fused;
+                          int F, int K, int N, int sample_rate, int amp_linear, hipStream_t st) {
+  // The frame-rate chain rule in the same launch (P and Q kept in LDS) was correct and slower: 60.1 us against 41.6 + 21.2 in two
+  // launches at batch 32, 215 against 135 + 66 at batch 128 (profiles/r05_harm_bwd_table.txt).
   const int W = K <= 100 ? 6 : (K <= 128 ? 8 : 10);
   const bt_u32x4* frags = bt_fragments(W);
   if (!frags) return DDSP_ERR_LAUNCH;
@@ -523,27 +452,12 @@ int launch_harm_bwd_table(const float* f0_hz, const double* theta0, const float*
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
     return v;
   }();
-  a.dbg = nullptr;
-#ifdef DDSP_BT_TIMELINE      // tools/exp_bwd_timeline.py's build only (the product does not take raw pointers from the environment)
-  { const char* e = getenv("DDSP_EXP_BT_TIMELINE"); a.dbg = e ? (long long*)strtoull(e, nullptr, 0) : nullptr; }
-#endif
-  a.amplitudes = amplitudes; a.hd = hd; a.grad_amp = grad_amp; a.grad_hd = grad_hd;
-  a.chain.F = F; a.chain.K = K; a.chain.N = N; a.chain.hop = a.hop;
-  a.chain.sample_rate = a.sample_rate; a.chain.nyquist = a.nyquist; a.chain.amp_linear = amp_linear;
-  a.chain.flags = flags; a.chain.inputs_are_controls = inputs_are_controls;
-  const int step = chain ? kBtFrames - 1 : kBtFrames;
-  const long groups = (a.rows + step - 1) / step;
+  const long groups = (a.rows + kBtFrames - 1) / kBtFrames;
   const dim3 grid((unsigned)std::min<long>(groups, 2L * n_cu));       // persistent: two blocks per CU (59 KB of LDS, 128 registers)
-  if (chain) {
-    if (W == 6) hipLaunchKernelGGL((harm_bwd_table_kernel<6, true>), grid, dim3(64 * kBtFrames), 0, st, a);
-    else if (W == 8) hipLaunchKernelGGL((harm_bwd_table_kernel<8, true>), grid, dim3(64 * kBtFrames), 0, st, a);
-    else hipLaunchKernelGGL((harm_bwd_table_kernel<10, true>), dim3(std::min<unsigned>(grid.x, (unsigned)n_cu)), dim3(1024), 0, st, a);
-  } else {
-    if (W == 6) hipLaunchKernelGGL((harm_bwd_table_kernel<6, false>), grid, dim3(64 * kBtFrames), 0, st, a);
-    else if (W == 8) hipLaunchKernelGGL((harm_bwd_table_kernel<8, false>), grid, dim3(64 * kBtFrames), 0, st, a);
-    else hipLaunchKernelGGL((harm_bwd_table_kernel<10, false>), dim3(std::min<unsigned>(grid.x, (unsigned)n_cu)), dim3(1024), 0, st, a);   // (one block of sixteen wavefronts per CU)
-  }
-  return hipGetLastError() == hipSuccess ? (chain ? 1 : DDSP_OK) : DDSP_ERR_LAUNCH;       // 1: the chain rule is done too
+  if (W == 6) hipLaunchKernelGGL((harm_bwd_table_kernel<6>), grid, dim3(64 * kBtFrames), 0, st, a);
+  else if (W == 8) hipLaunchKernelGGL((harm_bwd_table_kernel<8>), grid, dim3(64 * kBtFrames), 0, st, a);
+  else hipLaunchKernelGGL((harm_bwd_table_kernel<10>), dim3(std::min<unsigned>(grid.x, (unsigned)n_cu)), dim3(1024), 0, st, a);   // (one block of sixteen wavefronts per CU)
+  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
 }
 
 }  // namespace ddsp

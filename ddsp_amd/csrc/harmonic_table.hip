@@ -27,7 +27,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include "../../include/ddsp_amd.h"
@@ -152,21 +151,12 @@ template <> struct WtPoly<10> {      // 129 .. 200 harmonics on the same 512 poi
 // and on an fp64 prefix that is exact for any f0 a synthesiser sees; every product-sum is spelled out, so which
 // template instance a tile runs in cannot change a bit (tests/test_gpu_contract_shapes.py compares rows run alone, in a
 // batch of 32 and in a batch of 128).
-#ifndef DDSP_WT_WALKER
-#define DDSP_WT_WALKER 2
-#endif
-#ifndef DDSP_WT_SLOTS
-#define DDSP_WT_SLOTS 0x73256104u
-#endif
 // Which wavefront does what is chosen for the four SIMDs' totals, not the wavefronts': a SIMD issues for its four
 // wavefronts in turn, oldest first, and a tick ends when the busiest SIMD is done (r03n: the row maker next to
 // tabulator 3, whose SIMD also builds the phase tables, arrives at the barrier 900 clocks after the others).
-constexpr int kWtWalker = DDSP_WT_WALKER;        // the tabulator that walks the chunk descriptors
-#ifndef DDSP_WT_SIZER
-#define DDSP_WT_SIZER 0
-#endif
-constexpr int kWtSizer = DDSP_WT_SIZER;          // the tabulator that chooses the table sizes (wt_table_size)
-constexpr unsigned kWtSlots = DDSP_WT_SLOTS;     // nibble sw: the tile slot of interpolator sw (wavefront 4 + sw, SIMD sw % 4):
+constexpr int kWtWalker = 2;                     // the tabulator that walks the chunk descriptors
+constexpr int kWtSizer = 0;                      // the tabulator that chooses the table sizes (wt_table_size)
+constexpr unsigned kWtSlots = 0x73256104u;       // nibble sw: the tile slot of interpolator sw (wavefront 4 + sw, SIMD sw % 4):
                                                  // the slots that come up short (7, 6, then 5, 4) are SIMD 3's and SIMD 0's
 struct WtDesc { int b, j0, nfr, fresh; };        // a chunk: frames j0 .. j0 + nfr - 1 of row b; nfr == 0: none
 
@@ -182,7 +172,6 @@ struct TableArgs {
   int ragged;          // hop % 64 != 0: a frame's last tile is cut short (lanes past the frame's end store nothing)
   int rows16;          // rows of hd (and of the controls out) are 16 bytes apart and aligned: K % 4 == 0, aligned bases
   double inv_sr, inv_2hop, hop_d, half_hm1;
-  long long* dbg;      // DDSP_EXP_TABLE_TIMELINE=1: shader-clock stamps of block 0, [wavefront][tick + 2][stamp]; or null
 };
 
 struct WtWalk { int pos, pos_first, end, seg_left, base, rem, b, j; };
@@ -199,11 +188,7 @@ struct WtWalk { int pos, pos_first, end, seg_left, base, rem, b, j; };
 // batch.  So: a row is cut into SEGMENTS of kWtSegment frames at fixed positions (j / kWtSegment), T is a function of the
 // segment's f0 alone (the smallest over its frames and the one behind them: wt_table_size), and the walker never lets a chunk
 // straddle a segment boundary (two chunks of 31 frames per full segment).
-#if defined(DDSP_EXP_SEGMENT)
-constexpr int kWtSegment = DDSP_EXP_SEGMENT;       // experiment: other segment lengths (a huge one: no cuts)
-#else
 constexpr int kWtSegment = 2 * kWtFrames;
-#endif
 
 // the next chunk of the block's run of frames (one wavefront, wave-uniform arithmetic)
 __device__ __forceinline__ WtDesc wt_next_chunk(WtWalk& w, const TableArgs& p) {
@@ -263,51 +248,28 @@ __device__ __forceinline__ WtDesc wt_read_desc(const WtDesc* ring, int slot) {
 // window weight off in its low bits, the error of both table rows' accumulators in the same half - while a tabulator of the same
 // SIMD executes MFMAs: once in 10^6 .. 10^9 tiles for the shapes of the K <= 128 instances, in 5 - 20 % of all launches for the
 // 129 .. 200-harmonic instances (tools/stress_determinism.py reproduces it at will; with one extra vector load per tabulator and
-// tick, -DDDSP_EXP_T_DUMMY_LOADS=1, every launch of a frame-size-128 shape differs somewhere).  What it is NOT (each tested on
+// tick, every launch of a frame-size-128 shape differs somewhere).  What it is NOT (each tested on
 // the chip, profiles/r04_packed_fma_glitch.txt): a missing wait state around the statements (s_nop 1 in front of every one: no
 // change), a result pair placed on a source pair whose halves cross (early-clobber / tied constraints: no change), the
 // v_permlane32_swap of the wide instances' row makers, a load landing in a register still in use (the same statements without
 // the packed instructions: no event in any configuration), an LDS race (theta, z, the table offset and the envelope weight of a
 // differing sample are bit-equal between the two launches; only the accumulators' halves differ).  The same arithmetic as
 // plain v_fma_f32 - below - never showed an event, in the amplified configurations either, and costs 0.7 us of 36.6 at batch
-// 128 (nothing at batch 32): -DDDSP_EXP_PACKED_PHASE_B brings the assembly statements back for whoever wants to look again.
+// 128 (nothing at batch 32).
 // The compiler's own packed instructions in the row makers (v_pk_mul / v_pk_add / v_pk_fma_f32 of phase A, a dozen per row
 // pair between transcendentals) were never hit - not in 10^4 launches in which the interpolators were hit every time.
 // tests/test_isa_guards.py keeps assembly-statement packed FMAs out of the instruction stream.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#if defined(__AMDGCN__) && defined(DDSP_EXP_PACKED_PHASE_B)
-#define DDSP_WT_PK_ASM 1
-#else
-#define DDSP_WT_PK_ASM 0
-#endif
 // (e, o) <- (e, o) * z^2 + (ce, co), zz = (z, z^2)
 __device__ __forceinline__ f32x2 wt_pk_horner(f32x2 eo, f32x2 zz, f32x2 coef) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(eo), "v"(zz), "v"(coef));
-  return r;
-#else
   return (f32x2){fmaf(eo[0], zz[1], coef[0]), fmaf(eo[1], zz[1], coef[1])};
-#endif
 }
 // the window weights of a tap pair: (e + z o, e - z o)
 __device__ __forceinline__ f32x2 wt_pk_weights(f32x2 eo, f32x2 zz) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0] neg_hi:[0,1,0]" : "=v"(r) : "v"(eo), "v"(zz));
-  return r;
-#else
   return (f32x2){fmaf(eo[1], zz[0], eo[0]), fmaf(eo[1], -zz[0], eo[0])};
-#endif
 }
 __device__ __forceinline__ f32x2 wt_pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-#else
   return (f32x2){fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1])};
-#endif
 }
 // the fp16 pair (c2048[0] - 2048 h[0], c2048[1] - 2048 h[1]), c2048 = 2048 c: what hi = h leaves of c, scaled - the
 // differences are exact in fp32, the fp16 halves of h are read in place and the results written as fp16 halves
@@ -335,32 +297,14 @@ __device__ __forceinline__ int wt_floor_int(float x) {
 }
 // (a0 b1 + c0, a1 b0 + c1): the halves of b swapped
 __device__ __forceinline__ f32x2 wt_pk_fma_swap(f32x2 a, f32x2 b, f32x2 c) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-#else
   return (f32x2){fmaf(a[0], b[1], c[0]), fmaf(a[1], b[0], c[1])};
-#endif
 }
 // the window weights of two tap pairs at once, E = (e_a, e_b), O = (o_a, o_b): E + z O and E - z O
 __device__ __forceinline__ f32x2 wt_pk_plus(f32x2 o, f32x2 zz, f32x2 e) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(o), "v"(zz), "v"(e));
-  return r;
-#else
   return (f32x2){fmaf(o[0], zz[0], e[0]), fmaf(o[1], zz[0], e[1])};
-#endif
 }
 __device__ __forceinline__ f32x2 wt_pk_minus(f32x2 o, f32x2 zz, f32x2 e) {
-#if DDSP_WT_PK_ASM
-  f32x2 r;
-  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "v"(o), "v"(zz), "v"(e));
-  return r;
-#else
   return (f32x2){fmaf(-o[0], zz[0], e[0]), fmaf(-o[1], zz[0], e[1])};
-#endif
 }
 // the four 16-byte loads of a k-step have landed when at most N younger loads are still in flight (loads return in order)
 template <int N>
@@ -394,26 +338,17 @@ template <int W> struct WtPkCoefs {
         constexpr int s_ = decltype(ss)::value;
         constexpr float va = WtPoly<W>::e(pa, DE - s_), vb = WtPoly<W>::e(pb, DE - s_);
         e[g][s_] = (f32x2){va, vb};
-#if DDSP_WT_PK_ASM
-        DDSP_KEEP_IN_VGPR(e[g][s_]);          // resident: not re-made from literals at every use (a packed FMA takes no literal;
-#endif                                        // the plain FMAs do - v_fmaak_f32 -, and the coefficients need no registers)
       });
       wt_static_for<DO + 1>([&](auto ss) {
         constexpr int s_ = decltype(ss)::value;
         constexpr float va = WtPoly<W>::o(pa, DO - s_), vb = WtPoly<W>::o(pb, DO - s_);
         o[g][s_] = (f32x2){va, vb};
-#if DDSP_WT_PK_ASM
-        DDSP_KEEP_IN_VGPR(o[g][s_]);
-#endif
       });
     });
     wt_static_for<DE + 1>([&](auto ss) {
       constexpr int s_ = decltype(ss)::value;
       constexpr float ve = WtPoly<W>::e(0, DE - s_), vo = (DE - s_) <= DO ? WtPoly<W>::o(0, (DE - s_) <= DO ? DE - s_ : 0) : 0.0f;
       m[s_] = (f32x2){ve, vo};
-#if DDSP_WT_PK_ASM
-      if (MID) DDSP_KEEP_IN_VGPR(m[s_]);
-#endif
     });
   }
 };
@@ -517,12 +452,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
   const bool live = kq < K4;
   const float4* __restrict__ hd4 = reinterpret_cast<const float4*>(hd);
   const int mi = lane & 15, mg = lane >> 4;      // MFMA fragment coordinates
-#ifdef DDSP_WT_TIMELINE
-  const bool dbg_on = p.dbg != nullptr && blockIdx.x == 0 && lane == 0;
-#define DDSP_WT_STAMP(i) do { if (dbg_on && tick + 2 < 24) p.dbg[(wave * 24 + tick + 2) * 8 + (i)] = clock64(); } while (0)
-#else
-#define DDSP_WT_STAMP(i) do { } while (0)
-#endif
 
   // ---- the first two chunk descriptors (the walker), then everybody reads ----------------------------------------
   WtWalk walk;
@@ -669,7 +598,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
     if constexpr (!WIDE) { fetch_fragments(kWtT); frag_T = kWtT; }
     int Tm = kWtT, Tm_ahead = kWtT;                // the table size of the chunk this tick tabulates; the next tick's, read ahead
     for (int tick = -2;; ++tick) {
-      DDSP_WT_STAMP(0);
       if (rw == 3 && dM.nfr > 0) {
         if (dM.fresh) before = row_prefix(dM);
         fetch_f0(dM);
@@ -683,26 +611,10 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
           if (tick == -2 && dA.nfr > 0) fetch_segment(dA, pf_first);
         }
       }
-#if defined(DDSP_EXP_T_DUMMY_LOADS)     // experiment: vector memory loads of THIS wavefront landing while its MFMAs run
-      ddsp_f32x4 exp_dummy = {0.f, 0.f, 0.f, 0.f};
-      auto exp_dummy_issue = [&]() {
-        const float4* src = reinterpret_cast<const float4*>(&kWtFragSet6.t512.v[rw][0][0][0][0][0][0]) + lane;
-#pragma unroll
-        for (int i = 0; i < DDSP_EXP_T_DUMMY_LOADS; ++i) load_issue(exp_dummy, src + 64 * i);
-      };
-#if !defined(DDSP_EXP_T_DUMMY_AFTER)
-      exp_dummy_issue();
-#endif
-#if defined(DDSP_EXP_T_DUMMY_WAIT_BEFORE)     // .. but landed before the first MFMA
-      __asm__ volatile("s_waitcnt vmcnt(0)" : "+v"(exp_dummy));
-#endif
-#endif
       // ---------------- table of chunk tick + 1: O and E on the quarter range ---------------------------------------
       if constexpr (!WIDE) {
-#if !defined(DDSP_EXP_FORCE_T512)
         Tm_ahead = tsel[(tick + 2) & 3];           // chunk tick + 2, the next tick's: issued here, taken at the end of the tick
         if (tick == -1) Tm = __builtin_amdgcn_readfirstlane(tsel[0]);      // (the first chunk's was made in the tick before: no tick ahead of that)
-#endif
         if (dM.nfr > 0 && Tm != frag_T) {
           fetch_fragments(Tm);
           frag_T = Tm;
@@ -712,11 +624,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
           fragments_landed();
         }
       }
-#if defined(DDSP_EXP_NO_SMALL_PATH)
-      if (false) {
-#else
       if (dM.nfr > 0 && !WIDE && Tm != kWtT) {
-#endif
         // ---- 256, 128 or 64 points: T / 64 position tiles - tabulator rw has tile rw or none -, one k-step -------------------
         if (rw < (Tm >> 6)) {
           const int half = Tm >> 1;
@@ -837,13 +745,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
         }
        }
       }
-#if defined(DDSP_EXP_T_DUMMY_LOADS)
-#if defined(DDSP_EXP_T_DUMMY_AFTER)           // .. issued behind the last MFMA instead
-      exp_dummy_issue();
-#endif
-      __asm__ volatile("s_waitcnt vmcnt(0)" : "+v"(exp_dummy));
-#endif
-      DDSP_WT_STAMP(1);
       desc_issue((tick + 3) & 7);
       // ---------------- wavefront 3: the per-frame phase tables of chunk tick + 1 ---------------------------------------
       if (rw == 3) {
@@ -927,7 +828,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
         int lane_ = lane;
         DDSP_KEEP_IN_VGPR(lane_);
         if constexpr (!WIDE) {
-#if !defined(DDSP_EXP_NO_TSEL_COMPUTE)
           // (lanes 0 .. 62: the segment's frames and the one behind; a NaN is no minimum - fminf - and <= 0 keeps 512 points)
           if (dN.nfr > 0) {
             const int t_sel = wt_table_size(wave_min_dpp(lane_ <= kWtSegment ? pseg : __builtin_inff()), p.size_thr);
@@ -937,12 +837,8 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
             const int t_sel = wt_table_size(wave_min_dpp(lane_ <= kWtSegment ? pf_first : __builtin_inff()), p.size_thr);
             if (lane_ == 0) tsel[0] = t_sel;
           }
-#else
-          if (lane_ < 4) tsel[lane_] = kWtT;
-#endif
         }
       }
-      DDSP_WT_STAMP(2);
       // ---------------- the walker: the descriptor of chunk tick + 4 ---------------------------------------------------
       if (rw == kWtWalker) {
         const WtDesc dn = wt_next_chunk(walk, p);
@@ -953,9 +849,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
         Tm = __builtin_amdgcn_readfirstlane(Tm_ahead);
         if (tick == -2) fragments_landed();
       }
-      DDSP_WT_STAMP(3);
       __syncthreads();
-      DDSP_WT_STAMP(4);
       dB = dM; dM = dA; dA = dL;
       { const int t3 = pb; pb = pm; pm = pa; pa = t3; }
       if (tick + 1 >= 0 && dB.nfr == 0) break;
@@ -1136,7 +1030,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
       prefetch(dA, rows_a, 0);
       if constexpr (WIDE) prefetch(dA, rows_b, 1);
       auto one_tick = [&](int tick, Rows& cur, Rows& next) -> bool {
-        DDSP_WT_STAMP(0);
         desc_issue((tick + 3) & 7);
         desc_take();
         rows_landed(cur);                          // issued a tick ago
@@ -1144,21 +1037,15 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
           // cur = the first four rows, next = the other four, both fetched during the tick before; each set is
           // fetched again for the next chunk as soon as it has been used
           rows_landed(next);
-          DDSP_WT_STAMP(1);
-          DDSP_WT_STAMP(2);
           if (dA.nfr > 0) phase_a(dA, planes_all[pa], cur, 0);
           prefetch(dL, cur, 0);
           if (dA.nfr > 0) phase_a(dA, planes_all[pa], next, 1);
           prefetch(dL, next, 1);
         } else {
         prefetch(dL, next, 0);                     // the next tick's dA
-        DDSP_WT_STAMP(1);
-        DDSP_WT_STAMP(2);
         if (dA.nfr > 0) phase_a(dA, planes_all[pa], cur, 0);
         }
-        DDSP_WT_STAMP(3);
         __syncthreads();
-        DDSP_WT_STAMP(4);
         dB = dM; dM = dA; dA = dL;
         { const int t3 = pb; pb = pm; pm = pa; pa = t3; }
         return tick + 1 >= 0 && dB.nfr == 0;
@@ -1187,12 +1074,8 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
       float Tf = (float)kWtT;
       int t_ahead = kWtT;
       for (int tick = -2;; ++tick) {
-        DDSP_WT_STAMP(0);
         desc_issue((tick + 3) & 7);
-#if !defined(DDSP_EXP_FORCE_T512)
         if constexpr (!WIDE) t_ahead = tsel[(tick + 1) & 3];  // chunk tick + 1: the next tick's
-#endif
-        DDSP_WT_STAMP(1);
         if (dB.nfr > 0) {
           // ---------------- phase B of chunk tick: tiles of 64 samples, lanes = samples ----------------------------
           const int nfr = dB.nfr;
@@ -1313,17 +1196,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
             if (ADD)
 #pragma unroll
               for (int u = 0; u < NT; ++u) out[u] += addv[u];
-#if defined(DDSP_EXP_DEBUG_DUMP)       // experiment: the per-sample intermediates, eight floats per sample
-            if (p.dbg != nullptr) {
-              float* dump = reinterpret_cast<float*>(p.dbg);
-#pragma unroll
-              for (int u = 0; u < NT; ++u) {
-                float* d8 = dump + 8 * (chunk0 + (size_t)(tile * 64 + lane) + 512u * (size_t)u);
-                d8[0] = theta[u]; d8[1] = zz[u][0]; d8[2] = acc0[u][0]; d8[3] = acc0[u][1];
-                d8[4] = acc1[u][0]; d8[5] = acc1[u][1]; d8[6] = w_next[u]; d8[7] = (float)(t0[u] - tab);
-              }
-            }
-#endif
             if (!ragged) {
 #pragma unroll
               for (int u = 0; u < NT; ++u) *reinterpret_cast<float*>(out_chunk + (o32 + 2048u * (unsigned)u)) = out[u];          // N == F * hop
@@ -1342,19 +1214,15 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
             else if (cnt == 1) tiles(base + slot, std::integral_constant<int, 1>{});
           }
         }
-        DDSP_WT_STAMP(2);
         desc_take();
         if constexpr (!WIDE) Tf = (float)__builtin_amdgcn_readfirstlane(t_ahead);
-        DDSP_WT_STAMP(3);
         __syncthreads();
-        DDSP_WT_STAMP(4);
         dB = dM; dM = dA; dA = dL;
         { const int t3 = pb; pb = pm; pm = pa; pa = t3; }
         if (tick + 1 >= 0 && dB.nfr == 0) break;
       }
     }
   }
-#undef DDSP_WT_STAMP
 }
 
 bool harm_table_ok(int F, int K, int N, const void* hd, const void* ctl_amp, const void* ctl_hd, unsigned flags,
@@ -1434,20 +1302,6 @@ int launch_harm_table(const float* amplitudes, const float* hd, const float* f0,
   p.frames_per_block = (p.total_frames + blocks - 1) / blocks;
   blocks = (p.total_frames + p.frames_per_block - 1) / p.frames_per_block;       // no empty block
   const dim3 grid((unsigned)blocks), block(1024);
-  p.dbg = nullptr;
-#if defined(DDSP_EXP_DEBUG_DUMP)
-  if (const char* e = getenv("DDSP_EXP_DUMP_PTR")) p.dbg = reinterpret_cast<long long*>(strtoull(e, nullptr, 10));
-#endif
-#ifdef DDSP_WT_TIMELINE
-  // DDSP_EXP_TABLE_TIMELINE=1 (a -DDDSP_WT_TIMELINE build): block 0 records shader-clock stamps per tick
-  static const bool timeline = getenv("DDSP_EXP_TABLE_TIMELINE") != nullptr;
-  static long long* dbg_buf = nullptr;
-  if (timeline) {
-    if (!dbg_buf && hipMalloc(&dbg_buf, 16 * 24 * 8 * sizeof(long long)) != hipSuccess) dbg_buf = nullptr;
-    if (dbg_buf) (void)hipMemsetAsync(dbg_buf, 0, 16 * 24 * 8 * sizeof(long long), st);
-    p.dbg = dbg_buf;
-  }
-#endif
   hipEvent_t ev0, ev1;
   profile_kernel_events(kHarmTable, &ev0, &ev1);
 #define DDSP_LAUNCH_TABLE__(W, NK, ONE, ADD, R16)                                                                 \
@@ -1476,25 +1330,6 @@ int launch_harm_table(const float* amplitudes, const float* hd, const float* f0,
 #undef DDSP_LAUNCH_TABLE
 #undef DDSP_LAUNCH_TABLE_
 #undef DDSP_LAUNCH_TABLE__
-#ifdef DDSP_WT_TIMELINE
-  if (p.dbg) {
-    static long long host[16 * 24 * 8];
-    if (hipStreamSynchronize(st) == hipSuccess &&
-        hipMemcpy(host, p.dbg, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess) {
-      const long long t0 = host[0];
-      for (int w = 0; w < 16; ++w)
-        for (int i = 0; i < 24 && host[(w * 24 + i) * 8] != 0; ++i) {
-          const long long* r = host + (w * 24 + i) * 8;
-          if (w < 4)
-            fprintf(stderr, "[timeline] T%d tick %3d  start %8lld  mfma+table +%6lld  tables/desc +%6lld  barrier +%6lld\n", w, i - 2,
-                    r[0] - t0, r[1] - r[0], r[3] - r[1], r[4] - r[3]);
-          else
-            fprintf(stderr, "[timeline] S%-2d tick %3d  start %8lld  fetch +%6lld  phase B +%6lld  phase A +%6lld  barrier +%6lld\n", w - 4,
-                    i - 2, r[0] - t0, r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3]);
-        }
-    }
-  }
-#endif
   return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
 }
 

@@ -44,7 +44,6 @@
 #include "../../include/ddsp_amd.h"
 
 namespace ddsp {
-constexpr unsigned DDSP_CONV_EXP_PLAIN_ORDER = 1u << 30;      // internal: rv_fft_kernel deals its items in block order
 
 
 constexpr int kRvP = 4096;             // output samples per block = taps per IR partition
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(kRvThreads, 8) void rv_fft_kernel(const float* __re
   // are all but twelve of the items) 30.9 -> 29.9 us a launch at batch 128; with an impulse response per row - a third of the
   // items are partitions, which read half as much and overlap with nothing - an XCD's share of a round is all partitions or all
   // audio and the launch is 0.8 us slower at batch 32, no faster at 128: those keep the block order.
-  const bool xcd_order = (gridDim.x & 7) == 0 && p.pairs > 0 && !(p.flags & DDSP_CONV_EXP_PLAIN_ORDER);
+  const bool xcd_order = (gridDim.x & 7) == 0 && p.pairs > 0;
   int round_base = 0;
   auto item_of_round = [&]() -> int {              // this block's item of the round that starts at round_base, or n_items
     if (!xcd_order) return round_base + (int)blockIdx.x < n_items ? round_base + (int)blockIdx.x : n_items;
@@ -524,12 +523,8 @@ extern "C" int ddsp_fft_convolve_long_ex_f32(const float* audio, const float* im
   RvArgs p;
   p.N = N; p.L = L; p.n_out = n_out; p.nb = rv_blocks(n_out, delay); p.np = rv_parts(L); p.delay = delay;
   p.flags = flags; p.ir_batch = Bir;
-  static const bool plain_order = getenv("DDSP_EXP_RV_PLAIN_ORDER") != nullptr;     // (A/B of the item order, tools/exp_xcd_order.sh)
-  if (plain_order) p.flags |= DDSP_CONV_EXP_PLAIN_ORDER;
   // row pairs: one impulse response for at least two rows - the trainable Reverb of the shipped configurations, effects.py:62-80
-  // (DDSP_EXP_REVERB=single keeps the one-row form for the A/B)
-  static const bool single_env = [] { const char* e = getenv("DDSP_EXP_REVERB"); return e && e[0] == 's'; }();
-  const bool pair_mode = Bir == 1 && B >= 2 && !single_env;
+  const bool pair_mode = Bir == 1 && B >= 2;
   p.pairs = pair_mode ? (B + 1) / 2 : 0; p.B = B;
   if (pair_mode) p.nb = (n_out + delay + kRvP - 1) / kRvP;          // (no rounding up to even: a spectrum is one block)
   const int rows_z = pair_mode ? p.pairs : B;

@@ -403,16 +403,6 @@ __device__ __forceinline__ void sl_frames_to_spectra(float2* s, const float* __r
     if (SlPlan<H>::kWaveLocal) __syncthreads();
     return;
   }
-  // (DDSP_SL_NO_*: parts of the kernels compiled out for the time accounting of tools/exp_loss_ablation.sh - wrong results)
-#if defined(DDSP_SL_NO_LOAD) || defined(DDSP_SL_NO_FFT) || defined(DDSP_SL_UNFUSED)
-#ifndef DDSP_SL_NO_LOAD
-  sl_load_frames<S>(s, trow, arow, tid, f0, n_frames, N);
-#endif
-  __syncthreads();
-#ifndef DDSP_SL_NO_FFT
-  sl_forward<H>(s, tid, 2 * G, 0);
-#endif
-#else
   if constexpr (kSlFusedFirst<H>) {
     sl_load_stage1<S>(s, trow, arow, tid, f0, n_frames, N);
     sl_forward<H, true>(s, tid, 2 * G, 0);
@@ -421,7 +411,6 @@ __device__ __forceinline__ void sl_frames_to_spectra(float2* s, const float* __r
     __syncthreads();
     sl_forward<H>(s, tid, 2 * G, 0);
   }
-#endif
   if (SlPlan<H>::kWaveLocal) __syncthreads();                  // the bins of a frame are read by other wavefronts
 }
 
@@ -475,9 +464,6 @@ __device__ __forceinline__ void stft_l1_block(float2* s, double (*red)[kSlThread
     }
   };
   constexpr int LOG2Q = LOG2H - 1;                             // pairs per frame in the main loop: H / 2
-#ifdef DDSP_SL_NO_BINS
-  if (N == 12345)
-#endif
   for (int e = tid; e < G * (H / 2); e += kSlThreads) {
     const int g = e >> LOG2Q, k = e & (H / 2 - 1);
     if (f0 + g < n_frames) pair_of_bins(g, k, std::false_type{});
@@ -680,9 +666,6 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
       if (2 * k != H) s[SP(abase + ib)] = make_float2(ex + oy, ox - ey);          // Z'[H-k] = conj E' + i conj O'
     }
   };
-#ifdef DDSP_SL_NO_BINS
-  if (N == 12345)
-#endif
   for (int e = tid; e < G * (H / 2); e += kSlThreads) {
     const int g = e >> (LOG2H - 1), k = e & (H / 2 - 1);
     if (f0 + g < n_frames) pair_grad(g, k);
@@ -691,9 +674,7 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
     if (f0 + g < n_frames) pair_grad(g, H / 2);
   __syncthreads();
   // ---- unscaled inverse transform of the audio frames ------------------------------------------------
-#ifndef DDSP_SL_NO_INV
   sl_inverse<H>(s, tid, G, G);
-#endif
   if (SlPlan<H>::kWaveLocal) __syncthreads();
   // ---- window and overlap-add: g_x[2n] = 2 Re U[n], g_x[2n+1] = 2 Im U[n] ------------------------------
   // Gathered per output sample: the (up to) four frames of this block that cover it are summed from
@@ -708,7 +689,6 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
     // division by it (fastdiv) and the window by its own sine per frame
     const int hop = (int)hop_div.d;
     const float inv_F = 1.0f / (float)F;
-#if !defined(DDSP_EXP_SL_OLA_SINGLES)
     if ((hop & 1) == 0) {                                      // (every 3 * 2^k frame the fused path takes: hop = 3 * 2^(k - 2), k >= 4)
       // sample pairs, as below: four LDS reads per pair
       for (int pp = tid; pp < (G + 3) * (hop >> 1); pp += kSlThreads) {
@@ -731,7 +711,6 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
         if (n + 1 < N) unsafeAtomicAdd(&grow[n + 1], acc1);
       }
     } else
-#endif
     for (int pidx = tid; pidx < (G + 3) * hop; pidx += kSlThreads) {
       const long n = (long)f0 * hop + pidx;
       if (n >= N) continue;
@@ -750,13 +729,9 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
     }
   } else {
   constexpr int LOG2HOP = __builtin_ctz(HOP);
-#if !defined(DDSP_EXP_SL_OLA_SINGLES)
   // (round 6) a lane takes the sample PAIR (2 m, 2 m + 1): both sit in one element of the transform (Re, Im), so the four frames
   // that cover them cost four LDS reads per pair instead of eight - the same fused multiply-adds per sample in the same order
   static_assert((HOP & 1) == 0, "sample pairs do not straddle a hop");
-#ifdef DDSP_SL_NO_OLA
-  if (N == 12345)
-#endif
   for (int pp = tid; pp < (G + 3) * (HOP / 2); pp += kSlThreads) {
     const int pidx = 2 * pp;
     const int n = f0 * HOP + pidx;
@@ -781,44 +756,9 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
     // (one fp32 atomic per sample and block, every one of them: blocks of every FFT size run side by side since the end of
     // round 3.  Rounds 2-3 kept plain read-modify-writes for the samples a block owns among the blocks of ITS size - and
     // were no faster for it: 190 us against 182 with atomics throughout, profiles/r03v_*)
-#ifdef DDSP_SL_NO_ATOMIC
-    if (acc0 == 1234.5f) { grow[n] = acc0; grow[n + 1] = acc1; }
-#else
     unsafeAtomicAdd(&grow[n], acc0);
     if (n + 1 < N) unsafeAtomicAdd(&grow[n + 1], acc1);
-#endif
   }
-#else
-#ifdef DDSP_SL_NO_OLA
-  if (N == 12345)
-#endif
-  for (int pidx = tid; pidx < (G + 3) * HOP; pidx += kSlThreads) {
-    const int n = f0 * HOP + pidx;
-    if (n >= N) continue;
-    const int gp = pidx >> LOG2HOP, ir = pidx & (HOP - 1);
-    float acc = 0.0f;
-    // the window at i = ir + jj S/4: cos(x + jj pi/2) = cos x, -sin x, -cos x, sin x - one sine and one cosine for the four frames
-    const float wrev = (float)ir * (1.0f / (float)S);
-    const float hc = 0.5f * __builtin_amdgcn_cosf(wrev), hs = 0.5f * __builtin_amdgcn_sinf(wrev);
-    const float wj[4] = {sl_hann(wrev), 0.5f + hs, 0.5f + hc, 0.5f - hs};      // (the first quarter as the square: sl_hann)
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int g = gp - jj, i = ir + jj * HOP;               // frame g covers the sample at its index i
-      if (g >= 0 && g < G && f0 + g < n_frames) {
-        const float2 u = s[SP(((g + G) << LOG2H) + (i >> 1))];
-        acc = fmaf(2.0f * ((i & 1) ? u.y : u.x), wj[jj], acc);
-      }
-    }
-    // (one fp32 atomic per sample and block, every one of them: blocks of every FFT size run side by side since the end of
-    // round 3.  Rounds 2-3 kept plain read-modify-writes for the samples a block owns among the blocks of ITS size - and
-    // were no faster for it: 190 us against 182 with atomics throughout, profiles/r03v_*)
-#ifdef DDSP_SL_NO_ATOMIC
-    if (acc == 1234.5f) grow[n] = acc;
-#else
-    unsafeAtomicAdd(&grow[n], acc);
-#endif
-  }
-#endif
   }
   if (partial) {                                               // block-uniform
     const double sm = (double)wave_sum(dm_sum), sl = (double)wave_sum(dl_sum);
@@ -1317,8 +1257,7 @@ static inline bool sl_plan_grid(SlMulti& m, const Fin& fin, int B, int N, const 
   if (n_sizes == 0) return true;
   bool same = true;
   for (int i = 1; i < n_sizes; ++i) same = same && m.nbx[i] == m.nbx[0];
-  static const bool plain_order = getenv("DDSP_EXP_SL_PLAIN_ORDER") != nullptr;
-  if (same && !plain_order) {
+  if (same) {
     const long long units = (long long)B * m.nbx[0];
     const long long grid = 8ll * n_sizes * ((units + 7) / 8);
     if (units < (1ll << 28) && grid < (1ll << 31)) {

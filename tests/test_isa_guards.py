@@ -166,8 +166,7 @@ def test_no_vector_written_scalar_base_right_before_a_pinned_load(asm):
 def test_no_assembly_statement_packed_fma_in_phase_b(asm):
   """Round 4 (csrc/harmonic_table.hip, "phase B on pairs of fp32 values"; profiles/r04_packed_fma_glitch.txt): runs of v_pk_fma_f32
   issued from assembly statements in the interpolators came back wrong in the last sixteen lanes now and then while a tabulator of
-  the same SIMD ran MFMAs.  Phase B is plain v_fma_f32 since; the statements survive behind -DDDSP_EXP_PACKED_PHASE_B for
-  experiments and must not reach the product build."""
+  the same SIMD ran MFMAs.  Phase B is plain v_fma_f32 since, and such statements must not come back."""
   kernels = _kernels(asm)
   assert kernels
   for name, body in kernels.items():
