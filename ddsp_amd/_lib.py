@@ -104,6 +104,16 @@ SIGNATURES = {
     'ddsp_remove_above_nyquist_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_float, c_voidp]),
     'ddsp_angular_cumsum_workspace_bytes': (c_size_t, [c_int] * 3),
     'ddsp_angular_cumsum_f32': (c_int, [c_f32p] * 2 + [c_voidp, c_size_t] + [c_int] * 3 + [c_voidp]),
+    'ddsp_wavetable_f32': (c_int, [c_f32p] * 4 + [c_int] * 5 + [c_float, c_uint, c_voidp]),
+    'ddsp_wavetable_backward_workspace_bytes': (c_size_t, [c_int] * 5),
+    'ddsp_wavetable_backward_f32': (c_int, [c_f32p] * 7 + [c_voidp, c_size_t] + [c_int] * 5 + [c_float, c_uint, c_voidp]),
+    'ddsp_linear_lookup_f32': (c_int, [c_f32p] * 3 + [c_int] * 4 + [c_voidp]),
+    'ddsp_linear_lookup_backward_workspace_bytes': (c_size_t, [c_int] * 2),
+    'ddsp_linear_lookup_backward_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_variable_length_delay_f32': (c_int, [c_f32p] * 4 + [c_int] * 3 + [c_float] * 2 + [c_uint, c_voidp]),
+    'ddsp_variable_length_delay_backward_workspace_bytes': (c_size_t, [c_int] * 2),
+    'ddsp_variable_length_delay_backward_f32': (c_int, [c_f32p] * 7 + [c_voidp, c_size_t] + [c_int] * 3 + [c_float] * 2 +
+                                                [c_uint, c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),
@@ -122,6 +132,10 @@ NOISE_SCALE_EXP_SIGMOID = 0x1
 NOISE_FIR_VECTOR_ALU = 0x8
 NOISE_BITS_23 = 0x10
 DECAY_SCALE_EXP_SIGMOID = 0x1
+WT_SCALE_EXP_SIGMOID = 0x1
+DELAY_ADD_DRY = 0x1
+DELAY_GAIN_EXP_SIGMOID = 0x2
+DELAY_PHASE_SIGMOID = 0x4
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
 CONV_ADD_DRY = 0x1

@@ -858,3 +858,232 @@ def uniform_noise(batch_size, n_samples, seed=0, batch_offset=0, noise_bits=23):
                                              int(seed), int(batch_offset), int(noise_bits), _stream())
   _lib.check(rc, 'ddsp_uniform_noise_ex_f32')
   return out
+
+
+# --------------------------------------------------------------------------------------
+# wavetable synthesis and the variable-length delay  (ddsp/core.py:1167-1313)
+# --------------------------------------------------------------------------------------
+_wavetable_ws = Workspace()
+
+
+def _needs_grad(*tensors):
+  return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+def _lookup_shapes(phase, wavetables):
+  """phase [B,N,1] / [B,N] -> [B,N]; wavetables [B,W] / [B,1,W] / [B,N,W] -> [B,Fw,W] (ddsp/core.py:1184-1190)."""
+  if wavetables.dim() == 2:
+    wavetables = wavetables[:, None, :]
+  if phase.dim() == 3 and phase.shape[-1] == 1:
+    phase = phase[:, :, 0]
+  if phase.dim() != 2 or wavetables.dim() != 3:
+    raise ValueError('phase must be [batch, n_samples, 1] or [batch, n_samples] and wavetables [batch, n_samples, n_wavetable] '
+                     'or [batch, n_wavetable], got {} and {}'.format(tuple(phase.shape), tuple(wavetables.shape)))
+  b, n = phase.shape
+  if wavetables.shape[0] == 1 and b > 1:
+    wavetables = wavetables.expand(b, -1, -1)
+  if wavetables.shape[0] != b or wavetables.shape[1] not in (1, n) or wavetables.shape[2] < 1:
+    raise ValueError('wavetables {} do not broadcast against phase {}'.format(tuple(wavetables.shape), tuple(phase.shape)))
+  return phase.contiguous(), wavetables.contiguous()
+
+
+class _LinearLookupFunction(torch.autograd.Function):
+  """torch.autograd node of core.linear_lookup (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, phase, wavetables):
+    ctx.save_for_backward(phase, wavetables)
+    b, n = phase.shape
+    out = torch.empty((b, n), dtype=torch.float32, device=phase.device)
+    if out.numel():
+      rc = _lib.load().ddsp_linear_lookup_f32(phase.data_ptr(), wavetables.data_ptr(), out.data_ptr(), b, n,
+                                              wavetables.shape[1], wavetables.shape[2], _stream())
+      _lib.check(rc, 'ddsp_linear_lookup_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    phase, wavetables = ctx.saved_tensors
+    b, n = phase.shape
+    grad_out = tf_float32(grad_out)
+    grad_phase, grad_tables = torch.empty_like(phase), torch.empty_like(wavetables)
+    if grad_out.numel():
+      lib = _lib.load()
+      ws = _wavetable_ws.get(cached_workspace_bytes('ddsp_linear_lookup_backward_workspace_bytes', b, n), phase.device)
+      rc = lib.ddsp_linear_lookup_backward_f32(phase.data_ptr(), wavetables.data_ptr(), grad_out.data_ptr(),
+                                               grad_phase.data_ptr(), grad_tables.data_ptr(), ws.data_ptr(), ws.numel(), b, n,
+                                               wavetables.shape[1], wavetables.shape[2], _stream())
+      _lib.check(rc, 'ddsp_linear_lookup_backward_f32')
+    return grad_phase, grad_tables
+
+
+def linear_lookup(phase, wavetables):
+  """core.linear_lookup (ddsp/core.py:1167-1213): lookup from wavetables with linear interpolation, [batch, n_samples].
+
+  sum_i relu(1 - |phase W - i|) w[i mod W] over the W + 1 points of the table with its first sample appended, evaluated as
+  the two-point lerp it is (the reference builds three [batch, n_samples, W + 1] tensors).  The phase is not wrapped: outside
+  [0, 1] the result fades to 0 within one table step, as the reference's weights do.  Differentiable in both arguments."""
+  phase, wavetables = tf_float32(phase), tf_float32(wavetables)
+  phase2, tables3 = _lookup_shapes(phase, wavetables)
+  if _needs_grad(phase, wavetables):
+    return _LinearLookupFunction.apply(phase2, tables3)
+  return _LinearLookupFunction.forward(_NoCtx(), phase2, tables3)
+
+
+class _NoCtx:
+  """Stands in for the autograd context when nothing requires grad (the forward bodies are shared)."""
+
+  def save_for_backward(self, *tensors):
+    pass
+
+
+def _wavetable_shapes(frequencies, amplitudes, wavetables, n_samples):
+  """-> contiguous amplitudes [B,F,1], wavetables [B,Fw,W], frequencies [B,F,1]; the reference's ValueErrors."""
+  if wavetables.dim() == 2:
+    wavetables = wavetables[:, None, :]
+  if frequencies.dim() == 2:
+    frequencies = frequencies[:, :, None]
+  if amplitudes.dim() == 2:
+    amplitudes = amplitudes[:, :, None]
+  if wavetables.dim() != 3 or wavetables.shape[-1] < 1:
+    raise ValueError('wavetables must be [batch, n_wavetable] or [batch, n_frames, n_wavetable], got {}'.format(
+        tuple(wavetables.shape)))
+  if frequencies.dim() != 3 or frequencies.shape[-1] != 1 or amplitudes.dim() != 3 or amplitudes.shape[-1] != 1:
+    raise ValueError('frequencies and amplitudes must be [batch, n_frames, 1], got {} and {}'.format(
+        tuple(frequencies.shape), tuple(amplitudes.shape)))
+  amplitudes, wavetables, frequencies = _broadcast_batch(amplitudes, wavetables, frequencies)
+  b, f, _ = amplitudes.shape
+  _check_amp_method('window', f, int(n_samples))          # the amplitude envelope's own conditions (core.py:677-693)
+  if tuple(frequencies.shape) != (b, f, 1):
+    raise ValueError('frequencies {} and amplitudes {} must have the same batch size and number of frames'.format(
+        tuple(frequencies.shape), tuple(amplitudes.shape)))
+  if wavetables.shape[0] != b:
+    raise ValueError('wavetables {} must have the batch size of the amplitudes {}'.format(
+        tuple(wavetables.shape), tuple(amplitudes.shape)))
+  return amplitudes.contiguous(), wavetables.contiguous(), frequencies.contiguous()
+
+
+class _WavetableFunction(torch.autograd.Function):
+  """torch.autograd node of core.wavetable_synthesis / synths.Wavetable (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, amplitudes, wavetables, frequencies, n_samples, sample_rate, flags):
+    ctx.save_for_backward(amplitudes, wavetables, frequencies)
+    ctx.args = (int(n_samples), float(sample_rate), int(flags))
+    b, f, _ = amplitudes.shape
+    out = torch.empty((b, int(n_samples)), dtype=torch.float32, device=amplitudes.device)
+    if b:
+      rc = _lib.load().ddsp_wavetable_f32(amplitudes.data_ptr(), wavetables.data_ptr(), frequencies.data_ptr(), out.data_ptr(),
+                                          b, f, wavetables.shape[1], wavetables.shape[2], int(n_samples), float(sample_rate),
+                                          int(flags), _stream())
+      _lib.check(rc, 'ddsp_wavetable_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_audio):
+    amplitudes, wavetables, frequencies = ctx.saved_tensors
+    n_samples, sample_rate, flags = ctx.args
+    b, f, _ = amplitudes.shape
+    fw, w = wavetables.shape[1], wavetables.shape[2]
+    grad_audio = tf_float32(grad_audio)
+    g_amp, g_tab, g_f0 = torch.empty_like(amplitudes), torch.empty_like(wavetables), torch.empty_like(frequencies)
+    if b:
+      lib = _lib.load()
+      ws = _wavetable_ws.get(cached_workspace_bytes('ddsp_wavetable_backward_workspace_bytes', b, f, fw, w, n_samples),
+                             amplitudes.device)
+      rc = lib.ddsp_wavetable_backward_f32(amplitudes.data_ptr(), wavetables.data_ptr(), frequencies.data_ptr(),
+                                           grad_audio.data_ptr(), g_amp.data_ptr(), g_tab.data_ptr(), g_f0.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), b, f, fw, w, n_samples, sample_rate, flags, _stream())
+      _lib.check(rc, 'ddsp_wavetable_backward_f32')
+    return g_amp, g_tab, g_f0, None, None, None
+
+
+def _wavetable(frequencies, amplitudes, wavetables, n_samples, sample_rate, flags):
+  frequencies, amplitudes, wavetables = tf_float32(frequencies), tf_float32(amplitudes), tf_float32(wavetables)
+  amps3, tables3, freq3 = _wavetable_shapes(frequencies, amplitudes, wavetables, n_samples)
+  if _needs_grad(frequencies, amplitudes, wavetables):
+    return _WavetableFunction.apply(amps3, tables3, freq3, n_samples, sample_rate, flags)
+  return _WavetableFunction.forward(_NoCtx(), amps3, tables3, freq3, n_samples, sample_rate, flags)
+
+
+def wavetable_synthesis(frequencies, amplitudes, wavetables, n_samples=64000, sample_rate=16000):
+  """core.wavetable_synthesis (ddsp/core.py:1236-1283): monophonic wavetable synthesizer, [batch, n_samples].
+
+  frequencies, amplitudes [batch, n_frames, 1]; wavetables [batch, n_wavetable] (static) or [batch, n_table_frames,
+  n_wavetable] (resampled linearly to n_samples, as the reference does; n_table_frames is free).  The amplitude envelope
+  is the 'window' upsampling, the phase the exclusive cumulative sum of the linearly upsampled frequency in cycles,
+  wrapped to [0, 1).  One kernel per call; the tables are read at frame rate and no [batch, n_samples, n_wavetable] tensor
+  exists.  Differentiable in all three inputs."""
+  return _wavetable(frequencies, amplitudes, wavetables, n_samples, sample_rate, 0)
+
+
+class _DelayFunction(torch.autograd.Function):
+  """torch.autograd node of core.variable_length_delay / effects.ModDelay (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, phase, audio, gain, max_length, phase_scale, phase_offset, flags):
+    ctx.save_for_backward(phase, audio, gain)
+    ctx.args = (int(max_length), float(phase_scale), float(phase_offset), int(flags))
+    b, n = audio.shape
+    out = torch.empty_like(audio)
+    if out.numel():
+      rc = _lib.load().ddsp_variable_length_delay_f32(phase.data_ptr(), audio.data_ptr(),
+                                                      gain.data_ptr() if gain is not None else None, out.data_ptr(), b, n,
+                                                      int(max_length), float(phase_scale), float(phase_offset), int(flags),
+                                                      _stream())
+      _lib.check(rc, 'ddsp_variable_length_delay_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    phase, audio, gain = ctx.saved_tensors
+    max_length, phase_scale, phase_offset, flags = ctx.args
+    b, n = audio.shape
+    grad_out = tf_float32(grad_out)
+    g_phase, g_audio = torch.empty_like(phase), torch.empty_like(audio)
+    g_gain = torch.empty_like(gain) if gain is not None else None
+    if grad_out.numel():
+      lib = _lib.load()
+      ws = _wavetable_ws.get(cached_workspace_bytes('ddsp_variable_length_delay_backward_workspace_bytes', b, n), audio.device)
+      rc = lib.ddsp_variable_length_delay_backward_f32(
+          phase.data_ptr(), audio.data_ptr(), gain.data_ptr() if gain is not None else None, grad_out.data_ptr(),
+          g_phase.data_ptr(), g_audio.data_ptr(), g_gain.data_ptr() if g_gain is not None else None, ws.data_ptr(), ws.numel(),
+          b, n, max_length, phase_scale, phase_offset, flags, _stream())
+      _lib.check(rc, 'ddsp_variable_length_delay_backward_f32')
+    return g_phase, g_audio, g_gain, None, None, None, None
+
+
+def _delay(phase, audio, gain, max_length, phase_scale, phase_offset, flags):
+  """phase / gain [B,N,1] or [B,N], audio [B,N] -> [B,N] (the body of variable_length_delay and ModDelay.get_signal)."""
+  phase, audio = tf_float32(phase), tf_float32(audio)
+  gain = tf_float32(gain) if gain is not None else None
+  if audio.dim() != 2:
+    raise ValueError('audio must be [batch, n_samples], got {}'.format(tuple(audio.shape)))
+  b, n = audio.shape
+
+  def flat(x, name):
+    if x.dim() == 3 and x.shape[-1] == 1:
+      x = x[:, :, 0]
+    if x.dim() != 2 or x.shape[1] != n or x.shape[0] not in (1, b):
+      raise ValueError('{} must be [batch, n_samples, 1] or [batch, n_samples] for audio {}, got {}'.format(
+          name, tuple(audio.shape), tuple(x.shape)))
+    return x.expand(b, n).contiguous()
+
+  if int(max_length) < 1:
+    raise ValueError('max_length must be at least 1, got {}'.format(max_length))
+  phase2 = flat(phase, 'phase')
+  gain2 = flat(gain, 'gain') if gain is not None else None
+  audio2 = audio.contiguous()
+  if _needs_grad(phase, audio, gain):
+    return _DelayFunction.apply(phase2, audio2, gain2, max_length, phase_scale, phase_offset, flags)
+  return _DelayFunction.forward(_NoCtx(), phase2, audio2, gain2, max_length, phase_scale, phase_offset, flags)
+
+
+def variable_length_delay(phase, audio, max_length=512):
+  """core.variable_length_delay (ddsp/core.py:1286-1313): delay audio by a time-varying amount, [batch, n_samples].
+
+  phase in [0, 1] is a delay of 0 .. max_length samples, linearly interpolated between the two neighbouring taps, which are
+  read straight from `audio` (zero before the clip's start): the reference's [batch, n_samples, max_length] frame tensor is
+  never built.  As in the reference, the point at full phase is the appended wrap point and reads the UNDELAYED sample.
+  Differentiable in both arguments."""
+  return _delay(phase, audio, None, max_length, 1.0, 0.0, 0)

@@ -32,6 +32,7 @@ enum KernelId {
   kNoiseBwdMfma,
   kTvFirMfma,
   kNoiseIrGemm,
+  kWavetableFused,
   kNumKernels
 };
 

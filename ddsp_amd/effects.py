@@ -3,7 +3,8 @@
 SURVEY.md section 8(f) rank 1.  The reference convolves with one 131 072-point FFT per clip; here
 `core.fft_convolve_long` runs a partitioned overlap-save convolution with LDS-resident FFTs
 (csrc/reverb.hip).  FilteredNoiseReverb and FIRFilter are compositions of kernels that exist;
-ExpDecayReverb's impulse response has its own small kernels (csrc/general.hip); ModDelay is not built.
+ExpDecayReverb's impulse response has its own small kernels (csrc/general.hip); ModDelay reads its two taps per
+sample straight from the audio (csrc/wavetable.hip).
 """
 import torch
 
@@ -289,3 +290,91 @@ class FIRFilter(processors.Processor):
   def get_signal(self, audio, magnitudes):
     """Filter audio [batch, n_samples] with the time-varying FIR designed from `magnitudes`."""
     return core.frequency_filter(audio, magnitudes, window_size=self.window_size)
+
+
+class _SigmoidFunction(torch.autograd.Function):
+  """tf.nn.sigmoid as a torch.autograd node on ddsp_sigmoid_f32 / ddsp_sigmoid_backward_f32."""
+
+  @staticmethod
+  def forward(ctx, x):
+    ctx.save_for_backward(x)
+    out = torch.empty_like(x)
+    if x.numel():
+      _lib.check(_lib.load().ddsp_sigmoid_f32(x.data_ptr(), out.data_ptr(), x.numel(), core._stream()), 'ddsp_sigmoid_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    x, = ctx.saved_tensors
+    grad_out = tf_float32(grad_out)
+    grad_in = torch.empty_like(x)
+    if x.numel():
+      _lib.check(_lib.load().ddsp_sigmoid_backward_f32(x.data_ptr(), grad_out.data_ptr(), grad_in.data_ptr(), x.numel(),
+                                                       core._stream()), 'ddsp_sigmoid_backward_f32')
+    return grad_in
+
+
+def _sigmoid(x):
+  """tf.nn.sigmoid, ModDelay's default phase_scale_fn."""
+  return _SigmoidFunction.apply(tf_float32(x))
+
+
+class ModDelay(processors.Processor):
+  """Modulated delay times used in chorus, flanger, and vibrato effects (ddsp/effects.py:327-392).
+
+  __call__ with the default scale functions (or None) is one kernel: exp_sigmoid of the gain, sigmoid of the phase, the
+  phase mapping, the two-tap read, the gain and the dry signal.  Differentiable in audio, gain and phase.
+  """
+
+  def __init__(self,
+               center_ms=15.0,
+               depth_ms=10.0,
+               sample_rate=16000,
+               gain_scale_fn=core.exp_sigmoid,
+               phase_scale_fn=_sigmoid,
+               add_dry=True,
+               name='mod_delay'):
+    super().__init__(name=name)
+    self.center_ms = center_ms
+    self.depth_ms = depth_ms
+    self.sample_rate = sample_rate
+    self.gain_scale_fn = gain_scale_fn
+    self.phase_scale_fn = phase_scale_fn
+    self.add_dry = add_dry
+
+  def get_controls(self, audio, gain, phase):
+    """Network outputs -> {'audio', 'gain', 'phase'} with the two scale functions applied (effects.py:347-365)."""
+    if self.gain_scale_fn is not None:
+      gain = self.gain_scale_fn(gain)
+    if self.phase_scale_fn is not None:
+      phase = self.phase_scale_fn(phase)
+    return {'audio': audio, 'gain': gain, 'phase': phase}
+
+  def _geometry(self):
+    max_delay_ms = self.center_ms + self.depth_ms
+    max_length_samples = int(self.sample_rate / 1000.0 * max_delay_ms)
+    return max_length_samples, self.depth_ms / max_delay_ms, self.center_ms / max_delay_ms
+
+  def get_signal(self, audio, gain, phase):
+    """Controls -> modulated audio [batch, n_samples] (effects.py:367-392)."""
+    max_length, depth_phase, center_phase = self._geometry()
+    return core._delay(phase, audio, gain, max_length, depth_phase, center_phase,
+                       _lib.DELAY_ADD_DRY if self.add_dry else 0)
+
+  def call(self, audio, gain, phase, return_outputs_dict=False, **kwargs):
+    for k in ['training', 'mask']:
+      kwargs.pop(k, None)
+    if kwargs:
+      raise TypeError('unexpected keyword arguments: {}'.format(sorted(kwargs)))
+    fusable = (self.gain_scale_fn in (None, core.exp_sigmoid)) and (self.phase_scale_fn in (None, _sigmoid))
+    if return_outputs_dict or not fusable:
+      controls = self.get_controls(audio, gain, phase)
+      signal = self.get_signal(**controls)
+      return dict(signal=signal, controls=controls) if return_outputs_dict else signal
+    flags = _lib.DELAY_ADD_DRY if self.add_dry else 0
+    if self.gain_scale_fn is not None:
+      flags |= _lib.DELAY_GAIN_EXP_SIGMOID
+    if self.phase_scale_fn is not None:
+      flags |= _lib.DELAY_PHASE_SIGMOID
+    max_length, depth_phase, center_phase = self._geometry()
+    return core._delay(phase, audio, gain, max_length, depth_phase, center_phase, flags)

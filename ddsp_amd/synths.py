@@ -428,6 +428,51 @@ class _HarmonicFunction(torch.autograd.Function):
     return grad_amp, grad_hd, grad_f0, None, None, None
 
 
+class Wavetable(processors.Processor):
+  """Synthesize audio from a series of wavetables (synths.py:199-258).
+
+  __call__ is one fused kernel (exp_sigmoid of the controls, window envelope, phase, lookup) that reads the frame-rate
+  tables once: the reference's get_signal resamples them to [batch, n_samples, n_wavetable] first.  Differentiable in
+  amplitudes, wavetables and f0_hz.
+  """
+
+  def __init__(self,
+               n_samples=64000,
+               sample_rate=16000,
+               scale_fn=core.exp_sigmoid,
+               name='wavetable'):
+    super().__init__(name=name)
+    self.n_samples = n_samples
+    self.sample_rate = sample_rate
+    self.scale_fn = scale_fn
+
+  def get_controls(self, amplitudes, wavetables, f0_hz):
+    """Network outputs -> {'amplitudes', 'wavetables', 'f0_hz'}: scale_fn on amplitudes and wavetables (synths.py:213-238)."""
+    if self.scale_fn is not None:
+      amplitudes = self.scale_fn(amplitudes)
+      wavetables = self.scale_fn(wavetables)
+    return {'amplitudes': amplitudes, 'wavetables': wavetables, 'f0_hz': f0_hz}
+
+  def get_signal(self, amplitudes, wavetables, f0_hz):
+    """Controls -> audio [batch, n_samples] (synths.py:240-258).  Resampling the audio-rate tables to n_samples again
+    is the identity, so the reference's two steps equal wavetable_synthesis on the frame-rate tables."""
+    return core.wavetable_synthesis(frequencies=f0_hz, amplitudes=amplitudes, wavetables=wavetables,
+                                    n_samples=self.n_samples, sample_rate=self.sample_rate)
+
+  def call(self, amplitudes, wavetables, f0_hz, return_outputs_dict=False, **kwargs):
+    """get_signal(**get_controls(...)) as one C-ABI call when scale_fn is core.exp_sigmoid or None."""
+    for k in ['training', 'mask']:
+      kwargs.pop(k, None)
+    if kwargs:
+      raise TypeError('unexpected keyword arguments: {}'.format(sorted(kwargs)))
+    if return_outputs_dict or (self.scale_fn is not None and self.scale_fn is not core.exp_sigmoid):
+      controls = self.get_controls(amplitudes, wavetables, f0_hz)
+      signal = self.get_signal(**controls)
+      return dict(signal=signal, controls=controls) if return_outputs_dict else signal
+    flags = _lib.WT_SCALE_EXP_SIGMOID if self.scale_fn is core.exp_sigmoid else 0
+    return core._wavetable(f0_hz, amplitudes, wavetables, self.n_samples, self.sample_rate, flags)
+
+
 class FilteredNoise(processors.Processor):
   """Synthesize audio by filtering white noise (synths.py:149-196).
 

@@ -578,6 +578,58 @@ int ddsp_exp_sigmoid_f32(const float* in, float* out, size_t n, float exponent,
                          float max_value, float threshold, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Wavetable synthesis and the modulated delay (ddsp/core.py:1167-1313, ddsp/synths.py:199-258,
+ * ddsp/effects.py:327-392).  Nothing of size [B, N, W] or [B, N, max_length] is ever built.
+ *
+ * ddsp_wavetable_f32: synths.Wavetable / core.wavetable_synthesis.
+ *   amplitudes [B,F,1], f0_hz [B,F,1] (N % F == 0, F + 1 < N: the 'window' envelope's own conditions),
+ *   wavetables [B,Fw,W] with any Fw >= 1 (Fw == 1: a static table; Fw == N: one table per sample; otherwise
+ *   linearly resampled to N as core.resample does), audio [B,N] out.
+ *   flags: DDSP_WT_SCALE_EXP_SIGMOID applies core.exp_sigmoid to amplitudes and wavetables (Wavetable.get_controls).
+ *   Fw == F and W <= 8192 run the fused kernel with both frames' tables in LDS (wt_fused_kernel); the rest gathers.
+ * ddsp_wavetable_backward_f32: grad_audio [B,N] in; grad_amplitudes [B,F,1], grad_wavetables [B,Fw,W] and
+ *   grad_f0_hz [B,F,1] out (with the flag, through exp_sigmoid to the raw inputs).  W <= 16384.  Deterministic.
+ */
+#define DDSP_WT_SCALE_EXP_SIGMOID 0x1u
+int ddsp_wavetable_f32(const float* amplitudes, const float* wavetables, const float* f0_hz, float* audio, int B,
+                       int F, int Fw, int W, int N, float sample_rate, unsigned flags, void* stream);
+size_t ddsp_wavetable_backward_workspace_bytes(int B, int F, int Fw, int W, int N);
+int ddsp_wavetable_backward_f32(const float* amplitudes, const float* wavetables, const float* f0_hz,
+                                const float* grad_audio, float* grad_amplitudes, float* grad_wavetables,
+                                float* grad_f0_hz, void* workspace, size_t workspace_bytes, int B, int F, int Fw,
+                                int W, int N, float sample_rate, unsigned flags, void* stream);
+
+/* core.linear_lookup (ddsp/core.py:1167-1213): phase [B,N], wavetables [B,Fw,W] with Fw == 1 or Fw == N, out [B,N].
+ * out = sum_i relu(1 - |phase W - i|) w[i mod W] over the points i = 0 .. W: the phase is NOT wrapped, a phase
+ * outside [0, 1] fades to 0 within one table step.  The backward call gives dL/d phase [B,N] and
+ * dL/d wavetables [B,Fw,W] (W <= 16384). */
+int ddsp_linear_lookup_f32(const float* phase, const float* wavetables, float* out, int B, int N, int Fw, int W,
+                           void* stream);
+size_t ddsp_linear_lookup_backward_workspace_bytes(int B, int N);
+int ddsp_linear_lookup_backward_f32(const float* phase, const float* wavetables, const float* grad_out,
+                                    float* grad_phase, float* grad_wavetables, void* workspace,
+                                    size_t workspace_bytes, int B, int N, int Fw, int W, void* stream);
+
+/* core.variable_length_delay (ddsp/core.py:1286-1313) and effects.ModDelay.get_signal around it:
+ *   out = gain * lookup(phase * phase_scale + phase_offset) (+ audio with DDSP_DELAY_ADD_DRY),
+ * the lookup reading point i < max_length as audio[n - i] (0 before the clip) and point max_length as audio[n],
+ * the reference's appended wrap point.  phase, audio, out [B,N]; gain [B,N] or NULL (gain 1).
+ * DDSP_DELAY_GAIN_EXP_SIGMOID / DDSP_DELAY_PHASE_SIGMOID apply ModDelay.get_controls' default scale functions.
+ * Backward: grad_phase, grad_audio [B,N] out, grad_gain [B,N] out (NULL exactly when gain is).  Deterministic. */
+#define DDSP_DELAY_ADD_DRY 0x1u
+#define DDSP_DELAY_GAIN_EXP_SIGMOID 0x2u
+#define DDSP_DELAY_PHASE_SIGMOID 0x4u
+int ddsp_variable_length_delay_f32(const float* phase, const float* audio, const float* gain, float* out, int B, int N,
+                                   int max_length, float phase_scale, float phase_offset, unsigned flags,
+                                   void* stream);
+size_t ddsp_variable_length_delay_backward_workspace_bytes(int B, int N);
+int ddsp_variable_length_delay_backward_f32(const float* phase, const float* audio, const float* gain,
+                                            const float* grad_out, float* grad_phase, float* grad_audio,
+                                            float* grad_gain, void* workspace, size_t workspace_bytes, int B, int N,
+                                            int max_length, float phase_scale, float phase_offset, unsigned flags,
+                                            void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
