@@ -114,6 +114,14 @@ SIGNATURES = {
     'ddsp_variable_length_delay_backward_workspace_bytes': (c_size_t, [c_int] * 2),
     'ddsp_variable_length_delay_backward_f32': (c_int, [c_f32p] * 7 + [c_voidp, c_size_t] + [c_int] * 3 + [c_float] * 2 +
                                                 [c_uint, c_voidp]),
+    'ddsp_sinusoidal_controls_f32': (c_int, [c_f32p] * 4 + [c_size_t, c_int, c_int] + [c_float] * 3 + [c_uint, c_voidp]),
+    'ddsp_sinusoidal_controls_backward_f32': (c_int, [c_f32p] * 6 + [c_size_t, c_int, c_int] + [c_float] * 3 + [c_uint, c_voidp]),
+    'ddsp_sinusoidal_workspace_bytes': (c_size_t, [c_int] * 4),
+    'ddsp_sinusoidal_signal_f32': (c_int, [c_f32p] * 3 + [c_voidp, c_size_t] + [c_int] * 4 + [c_float, c_uint, c_voidp]),
+    'ddsp_sinusoidal_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t] + [c_int] * 5 + [c_float] * 3 + [c_uint, c_voidp]),
+    'ddsp_sinusoidal_backward_workspace_bytes': (c_size_t, [c_int] * 4),
+    'ddsp_sinusoidal_backward_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t] + [c_int] * 5 + [c_float] * 3 + [c_uint, c_voidp]),
+    'ddsp_unit_convert_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),
@@ -136,6 +144,14 @@ WT_SCALE_EXP_SIGMOID = 0x1
 DELAY_ADD_DRY = 0x1
 DELAY_GAIN_EXP_SIGMOID = 0x2
 DELAY_PHASE_SIGMOID = 0x4
+SIN_AMP_EXP_SIGMOID = 0x1
+SIN_FREQ_SIGMOID = 0x2
+SIN_FREQ_SOFTMAX = 0x4
+SIN_MASK_NYQUIST = 0x8
+SIN_AMP_LINEAR = 0x10
+SIN_MAX_SIGMOID_DEPTH = 64
+CONVERT_OPS = {'midi_to_hz': 0, 'midi_to_hz_zero_silence': 1, 'hz_to_midi': 2, 'unit_to_midi': 3, 'unit_to_midi_clip': 4,
+               'midi_to_unit': 5, 'midi_to_unit_clip': 6, 'logb': 7}
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
 CONV_ADD_DRY = 0x1

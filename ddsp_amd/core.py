@@ -1087,3 +1087,147 @@ def variable_length_delay(phase, audio, max_length=512):
   never built.  As in the reference, the point at full phase is the appended wrap point and reads the UNDELAYED sample.
   Differentiable in both arguments."""
   return _delay(phase, audio, None, max_length, 1.0, 0.0, 0)
+
+
+# --------------------------------------------------------------------------------------
+# unit / MIDI / Hz conversions and the frequency scale functions  (ddsp/core.py:219-348, 414-507)
+# --------------------------------------------------------------------------------------
+def _convert(op, x, p0=0.0, p1=0.0):
+  x = tf_float32(x)
+  require_no_grad('core.' + op.replace('_clip', '').replace('_zero_silence', ''), x)
+  out = torch.empty_like(x)
+  if x.numel():
+    rc = _lib.load().ddsp_unit_convert_f32(x.data_ptr(), out.data_ptr(), x.numel(), _lib.CONVERT_OPS[op], float(p0), float(p1),
+                                           _stream())
+    _lib.check(rc, 'ddsp_unit_convert_f32')
+  return out
+
+
+def logb(x, base=2.0, eps=1e-5):
+  """core.logb (ddsp/core.py:219-221): safe_log(x, eps) / safe_log(base, eps), the divisor made safe the same way."""
+  den = math.log(eps if base <= 0.0 else base)
+  return _convert('logb', x, eps if den == 0.0 else den, eps)
+
+
+def midi_to_hz(notes, midi_zero_silence=False):
+  """core.midi_to_hz (ddsp/core.py:280-297): 440 * 2^((notes - 69) / 12); MIDI 0 -> 0 Hz with midi_zero_silence."""
+  return _convert('midi_to_hz_zero_silence' if midi_zero_silence else 'midi_to_hz', notes)
+
+
+def hz_to_midi(frequencies):
+  """core.hz_to_midi (ddsp/core.py:300-306): 12 (log2 f - log2 440) + 69, frequencies <= 0 map to MIDI 0."""
+  return _convert('hz_to_midi', frequencies)
+
+
+def _hz_to_midi_number(hz):
+  hz = float(hz)
+  return 0.0 if hz <= 0.0 else 12.0 * (math.log2(hz) - math.log2(440.0)) + 69.0
+
+
+def unit_to_midi(unit, midi_min=20.0, midi_max=90.0, clip=False):
+  """core.unit_to_midi (ddsp/core.py:309-315): the unit interval [0, 1] to MIDI notes."""
+  return _convert('unit_to_midi_clip' if clip else 'unit_to_midi', unit, midi_min, midi_max)
+
+
+def midi_to_unit(midi, midi_min=20.0, midi_max=90.0, clip=False):
+  """core.midi_to_unit (ddsp/core.py:318-324): MIDI notes to the unit interval [0, 1]."""
+  return _convert('midi_to_unit_clip' if clip else 'midi_to_unit', midi, midi_min, midi_max)
+
+
+def unit_to_hz(unit, hz_min, hz_max, clip=False):
+  """core.unit_to_hz (ddsp/core.py:327-336): [0, 1] to [hz_min, hz_max] on a logarithmic scale (the bounds are numbers)."""
+  return midi_to_hz(unit_to_midi(unit, _hz_to_midi_number(hz_min), _hz_to_midi_number(hz_max), clip))
+
+
+def hz_to_unit(hz, hz_min, hz_max, clip=False):
+  """core.hz_to_unit (ddsp/core.py:339-348): [hz_min, hz_max] to [0, 1] on a logarithmic scale (the bounds are numbers)."""
+  return midi_to_unit(hz_to_midi(hz), _hz_to_midi_number(hz_min), _hz_to_midi_number(hz_max), clip)
+
+
+def _depth_layout(freqs, depth):
+  """[B, T, K * depth] or [B, T, K, depth] -> (contiguous [B, T, K * depth], K, depth) (ddsp/core.py:414-420, 441-445)."""
+  if freqs.dim() == 4:
+    b, t, k, depth = freqs.shape
+    return freqs.reshape(b, t, k * depth).contiguous(), int(k), int(depth)
+  if freqs.dim() != 3:
+    raise ValueError('freqs must be [batch, time, n_sinusoids * depth] or [batch, time, n_sinusoids, depth], got {}'.format(
+        tuple(freqs.shape)))
+  depth = int(depth)
+  if depth < 1 or freqs.shape[-1] % depth != 0:
+    raise ValueError('the last axis of freqs ({}) is not a multiple of depth ({})'.format(freqs.shape[-1], depth))
+  return freqs.contiguous(), int(freqs.shape[-1]) // depth, depth
+
+
+class _FrequencyScaleFunction(torch.autograd.Function):
+  """torch.autograd node of core.frequencies_sigmoid / frequencies_softmax (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, freqs, k, depth, hz_min, hz_max, flag):
+    ctx.save_for_backward(freqs)
+    ctx.args = (k, depth, hz_min, hz_max, flag)
+    b, t, _ = freqs.shape
+    out = torch.empty((b, t, k), dtype=torch.float32, device=freqs.device)
+    if out.numel():
+      rc = _lib.load().ddsp_sinusoidal_controls_f32(None, freqs.data_ptr(), None, out.data_ptr(), b * t, k, depth, hz_min, hz_max,
+                                                    2.0, flag, _stream())
+      _lib.check(rc, 'ddsp_sinusoidal_controls_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    freqs, = ctx.saved_tensors
+    k, depth, hz_min, hz_max, flag = ctx.args
+    b, t, _ = freqs.shape
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty_like(freqs)
+    if grad.numel():
+      rc = _lib.load().ddsp_sinusoidal_controls_backward_f32(None, freqs.data_ptr(), None, grad_out.data_ptr(), None, grad.data_ptr(),
+                                                             b * t, k, depth, hz_min, hz_max, 2.0, flag, _stream())
+      _lib.check(rc, 'ddsp_sinusoidal_controls_backward_f32')
+    return grad, None, None, None, None, None
+
+
+def _frequency_scale(freqs, depth, hz_min, hz_max, flag):
+  raw = tf_float32(freqs)
+  flat, k, depth = _depth_layout(raw, depth)
+  if flag == _lib.SIN_FREQ_SIGMOID and depth > _lib.SIN_MAX_SIGMOID_DEPTH:
+    raise NotImplementedError('frequencies_sigmoid takes up to {} terms per sinusoid on the MI355X path, got depth={}'.format(
+        _lib.SIN_MAX_SIGMOID_DEPTH, depth))
+  args = (flat, k, depth, float(hz_min), float(hz_max), flag)
+  if _needs_grad(raw):
+    return _FrequencyScaleFunction.apply(*args)
+  return _FrequencyScaleFunction.forward(_NoCtx(), *args)
+
+
+def frequencies_softmax(freqs, depth=1, hz_min=20.0, hz_max=8000.0):
+  """core.frequencies_softmax (ddsp/core.py:423-456): softmax over `depth` network outputs per sinusoid, the expected
+  position on a unit grid mapped logarithmically to [hz_min, hz_max] Hz.  freqs [batch, time, n_sinusoids * depth] or
+  [batch, time, n_sinusoids, depth] -> [batch, time, n_sinusoids].  One kernel; differentiable."""
+  return _frequency_scale(freqs, depth, hz_min, hz_max, _lib.SIN_FREQ_SOFTMAX)
+
+
+def frequencies_sigmoid(freqs, depth=1, hz_min=0.0, hz_max=8000.0):
+  """core.frequencies_sigmoid (ddsp/core.py:459-507): a sum of `depth` sigmoids per sinusoid, each mapped logarithmically to
+  its share of [hz_min, hz_max] (the shares shrink by a constant factor; their bounds are host-side constants).  Shapes
+  as frequencies_softmax.  One kernel; differentiable; depth <= 64."""
+  return _frequency_scale(freqs, depth, hz_min, hz_max, _lib.SIN_FREQ_SIGMOID)
+
+
+def harmonic_to_sinusoidal(harm_amp, harm_dist, f0_hz, sample_rate=16000):
+  """core.harmonic_to_sinusoidal (ddsp/core.py:784-794): controls of a harmonic synth -> (amplitudes, frequencies) of a
+  sinusoidal one, both [batch, n_frames, n_harmonics]: harmonics at or above Nyquist removed, the distribution
+  renormalised, multiplied by the amplitude."""
+  harm_amp, harm_dist, f0_hz = tf_float32(harm_amp), tf_float32(harm_dist), tf_float32(f0_hz)
+  require_no_grad('core.harmonic_to_sinusoidal', harm_amp, harm_dist, f0_hz)
+  if harm_dist.dim() == 3 and harm_amp.dim() < 3:        # the reference multiplies: a number broadcasts (core_test.py:98)
+    harm_amp = harm_amp.reshape((1,) * (3 - harm_amp.dim()) + tuple(harm_amp.shape)).expand(
+        harm_dist.shape[0], harm_dist.shape[1], 1).contiguous()
+  harm_amp, harm_dist, f0_hz = _broadcast_batch(harm_amp, harm_dist, f0_hz)
+  b, f, k = _check_harmonic_shapes(harm_amp, harm_dist, f0_hz)
+  harm_dist = normalize_harmonics(harm_dist, f0_hz, sample_rate)
+  freqs, amps = torch.empty_like(harm_dist), torch.empty_like(harm_dist)
+  if freqs.numel():
+    rc = _lib.load().ddsp_harmonic_envelopes_f32(harm_amp.data_ptr(), harm_dist.data_ptr(), f0_hz.data_ptr(), None, freqs.data_ptr(),
+                                                 amps.data_ptr(), b, f, k, _stream())
+    _lib.check(rc, 'ddsp_harmonic_envelopes_f32')
+  return amps, freqs

@@ -996,3 +996,23 @@ extern "C" int ddsp_mix_f32(const float* signal_one, const float* signal_two, co
                      signal_one, signal_two, mix_level, out, rows, C);
   return check_launch();
 }
+
+// A library linked from a subset of the translation units (the test builds that add one kernel file to a fixed list) still
+// exports every symbol of the header: the entry points of csrc/sinusoidal.hip have weak stand-ins here that answer
+// DDSP_ERR_UNSUPPORTED (a size query: 0).  In libddsp_amd.so the definitions of sinusoidal.hip take their place.
+#define DDSP_WEAK extern "C" __attribute__((weak))
+DDSP_WEAK int ddsp_sinusoidal_controls_f32(const float*, const float*, float*, float*, size_t, int, int, float, float, float, unsigned,
+                                           void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinusoidal_controls_backward_f32(const float*, const float*, const float*, const float*, float*, float*, size_t, int,
+                                                    int, float, float, float, unsigned, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK size_t ddsp_sinusoidal_workspace_bytes(int, int, int, int) { return 0; }
+DDSP_WEAK int ddsp_sinusoidal_signal_f32(const float*, const float*, float*, void*, size_t, int, int, int, int, float, unsigned, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_sinusoidal_f32(const float*, const float*, float*, float*, float*, void*, size_t, int, int, int, int, int, float, float,
+                                  float, unsigned, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK size_t ddsp_sinusoidal_backward_workspace_bytes(int, int, int, int) { return 0; }
+DDSP_WEAK int ddsp_sinusoidal_backward_f32(const float*, const float*, const float*, float*, float*, void*, size_t, int, int, int, int, int,
+                                           float, float, float, unsigned, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_unit_convert_f32(const float*, float*, size_t, int, float, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+#undef DDSP_WEAK

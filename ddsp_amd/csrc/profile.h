@@ -33,6 +33,8 @@ enum KernelId {
   kTvFirMfma,
   kNoiseIrGemm,
   kWavetableFused,
+  kSinSynth,
+  kSinBwdSums,
   kNumKernels
 };
 

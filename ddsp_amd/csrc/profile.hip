@@ -20,7 +20,7 @@ const char* const kNames[kNumKernels] = {
     "rv_ifft_kernel", "stft_l1_kernel", "harm_bwd_pq_kernel", "harm_bwd_chain_kernel",
     "noise_bwd_taps_kernel", "noise_bwd_mags_kernel", "stft_l1_bwd_kernel", "harm_table_kernel",
     "noise_mfma65_kernel", "harm_bwd_table_kernel", "noise_bwd_mfma_kernel", "tv_fir_mfma_kernel", "noise_ir_gemm_kernel",
-    "wt_fused_kernel"};
+    "wt_fused_kernel", "sin_synth_kernel", "sin_bwd_sums_kernel"};
 static_assert(kNumKernels <= 32, "the selection mask is 32 bits");
 }  // namespace
 

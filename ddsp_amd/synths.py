@@ -3,6 +3,8 @@
 Constructor kwargs, defaults, `get_controls` / `get_signal` / `__call__` signatures and
 the controls-dict keys are the reference's.  Arithmetic: HIP kernels only.
 """
+import functools
+
 import torch
 
 from ddsp_amd import _lib
@@ -471,6 +473,312 @@ class Wavetable(processors.Processor):
       return dict(signal=signal, controls=controls) if return_outputs_dict else signal
     flags = _lib.WT_SCALE_EXP_SIGMOID if self.scale_fn is core.exp_sigmoid else 0
     return core._wavetable(f0_hz, amplitudes, wavetables, self.n_samples, self.sample_rate, flags)
+
+
+class Sinusoidal(processors.Processor):
+  """Synthesize audio with a bank of arbitrary sinusoidal oscillators (synths.py:260-323).
+
+  Amplitudes and frequencies on one frame grid with n_samples a multiple of the frame count, 'window' or 'linear'
+  amplitude envelopes: closed-form kernels at frame rate plus one synthesis kernel; no [batch, n_samples, n_sinusoids]
+  envelope exists (csrc/sinusoidal.hip).  Everything else the reference accepts ('nearest' / 'cubic', n_samples that is
+  not a multiple, different frame counts for the two inputs) follows its own chain core.resample + core.oscillator_bank
+  on materialised envelopes.  __call__ and get_signal are differentiable in both inputs on either path.
+
+  amp_scale_fn core.exp_sigmoid and freq_scale_fn core.frequencies_sigmoid / core.frequencies_softmax (or a
+  functools.partial of one with depth / hz_min / hz_max) are fused into the controls kernel; any other callable runs as
+  given on device tensors, and gradients then flow through it only if it is differentiable itself.
+  """
+
+  def __init__(self,
+               n_samples=64000,
+               sample_rate=16000,
+               amp_scale_fn=core.exp_sigmoid,
+               amp_resample_method='window',
+               freq_scale_fn=core.frequencies_sigmoid,
+               name='sinusoidal'):
+    super().__init__(name=name)
+    self.n_samples = n_samples
+    self.sample_rate = sample_rate
+    self.amp_scale_fn = amp_scale_fn
+    self.amp_resample_method = amp_resample_method
+    self.freq_scale_fn = freq_scale_fn
+    self._ws = core.Workspace()
+    self._ws_bwd = core.Workspace()
+
+  # -- what the scale functions are ----------------------------------------------------
+  _FREQ_FNS = ((core.frequencies_sigmoid, _lib.SIN_FREQ_SIGMOID, (1, 0.0, 8000.0)),
+               (core.frequencies_softmax, _lib.SIN_FREQ_SOFTMAX, (1, 20.0, 8000.0)))
+
+  def _freq_spec(self):
+    """(flag, depth, hz_min, hz_max) when freq_scale_fn is one of the two core functions or a functools.partial of one
+    with keyword arguments only; (0, 1, 0, 0) for None; None for a callable this class cannot see through."""
+    fn = self.freq_scale_fn
+    if fn is None:
+      return 0, 1, 0.0, 0.0
+    kw = {}
+    if isinstance(fn, functools.partial) and not fn.args and set(fn.keywords) <= {'depth', 'hz_min', 'hz_max'}:
+      fn, kw = fn.func, fn.keywords
+    for known, flag, (depth, hz_min, hz_max) in self._FREQ_FNS:
+      if fn is known:
+        depth = int(kw.get('depth', depth))
+        if flag == _lib.SIN_FREQ_SIGMOID and depth > _lib.SIN_MAX_SIGMOID_DEPTH:
+          return None                                     # the public function says so itself
+        return flag, depth, float(kw.get('hz_min', hz_min)), float(kw.get('hz_max', hz_max))
+    return None
+
+  def _prescale(self, amplitudes, frequencies):
+    """Runs the callables the kernels do not fuse; returns (amplitudes, frequencies [B,F,K*depth], flags, depth, hz_min, hz_max)
+    for the controls kernel."""
+    amplitudes, frequencies = core.tf_float32(amplitudes), core.tf_float32(frequencies)
+    flags = 0
+    if self.amp_scale_fn is core.exp_sigmoid:
+      flags |= _lib.SIN_AMP_EXP_SIGMOID
+    elif self.amp_scale_fn is not None:
+      amplitudes = core.tf_float32(self.amp_scale_fn(amplitudes))
+    spec = self._freq_spec()
+    if spec is None:
+      frequencies = core.tf_float32(self.freq_scale_fn(frequencies))
+      spec = (0, 1, 0.0, 0.0)
+    flag, depth, hz_min, hz_max = spec
+    if flag:
+      frequencies, _, depth = core._depth_layout(frequencies, depth)
+    if self.freq_scale_fn is not None:
+      flags |= _lib.SIN_MASK_NYQUIST                      # get_controls masks whenever it has a frequency scale function
+    return amplitudes, frequencies, flags | flag, depth, hz_min, hz_max
+
+  def _method_flag(self):
+    return _lib.SIN_AMP_LINEAR if self.amp_resample_method == 'linear' else 0
+
+  @staticmethod
+  def _check_3d(amplitudes, frequencies):
+    if amplitudes.dim() != 3 or frequencies.dim() != 3:
+      raise ValueError('amplitudes and frequencies must be [batch, n_frames, n_sinusoids], got {} and {}'.format(
+          tuple(amplitudes.shape), tuple(frequencies.shape)))
+
+  def _controls(self, amplitudes, frequencies, flags, depth, hz_min, hz_max):
+    """The controls kernel on prescaled inputs -> (ctl_amplitudes, ctl_frequencies).  With no frequency scale function the
+    two inputs may sit on different frame grids (nothing relates them at frame rate): the amplitudes are scaled alone."""
+    self._check_3d(amplitudes, frequencies)
+    lib = _lib.load()
+    if not flags:
+      return amplitudes, frequencies
+    b, f, k = amplitudes.shape
+    if tuple(frequencies.shape) != (b, f, k * depth):
+      if flags & ~_lib.SIN_AMP_EXP_SIGMOID:
+        raise ValueError('amplitudes {} and frequencies {} must share batch, frames and sinusoids (depth {})'.format(
+            tuple(amplitudes.shape), tuple(frequencies.shape), depth))
+      ctl_amp = torch.empty_like(amplitudes)
+      if ctl_amp.numel():
+        rc = lib.ddsp_sinusoidal_controls_f32(amplitudes.data_ptr(), amplitudes.data_ptr(), ctl_amp.data_ptr(),
+                                              torch.empty_like(amplitudes).data_ptr(), b * f, k, 1, 0.0, 0.0,
+                                              float(self.sample_rate), flags, core._stream())
+        _lib.check(rc, 'ddsp_sinusoidal_controls_f32')
+      return ctl_amp, frequencies
+    ctl_amp = torch.empty_like(amplitudes)
+    ctl_freq = torch.empty((b, f, k), dtype=torch.float32, device=amplitudes.device)
+    if ctl_amp.numel():
+      rc = lib.ddsp_sinusoidal_controls_f32(amplitudes.data_ptr(), frequencies.data_ptr(), ctl_amp.data_ptr(), ctl_freq.data_ptr(),
+                                            b * f, k, depth, hz_min, hz_max, float(self.sample_rate), flags, core._stream())
+      _lib.check(rc, 'ddsp_sinusoidal_controls_f32')
+    return ctl_amp, ctl_freq
+
+  def _controls_backward(self, amplitudes, frequencies, grad_ctl_amp, grad_ctl_freq, flags, depth, hz_min, hz_max):
+    if not flags:
+      return grad_ctl_amp, grad_ctl_freq
+    lib = _lib.load()
+    b, f, k = amplitudes.shape
+    grad_amp = torch.empty_like(amplitudes)
+    if tuple(frequencies.shape) != (b, f, k * depth):           # the amplitudes alone (see _controls)
+      scratch = torch.empty_like(amplitudes)
+      rc = lib.ddsp_sinusoidal_controls_backward_f32(amplitudes.data_ptr(), amplitudes.data_ptr(), grad_ctl_amp.data_ptr(), None,
+                                                     grad_amp.data_ptr(), scratch.data_ptr(), b * f, k, 1, 0.0, 0.0,
+                                                     float(self.sample_rate), flags, core._stream())
+      _lib.check(rc, 'ddsp_sinusoidal_controls_backward_f32')
+      return grad_amp, grad_ctl_freq
+    grad_freq = torch.empty_like(frequencies)
+    rc = lib.ddsp_sinusoidal_controls_backward_f32(amplitudes.data_ptr(), frequencies.data_ptr(), grad_ctl_amp.data_ptr(),
+                                                   grad_ctl_freq.data_ptr(), grad_amp.data_ptr(), grad_freq.data_ptr(), b * f, k,
+                                                   depth, hz_min, hz_max, float(self.sample_rate), flags, core._stream())
+    _lib.check(rc, 'ddsp_sinusoidal_controls_backward_f32')
+    return grad_amp, grad_freq
+
+  def _on_fused_kernels(self, amp_shape, freq_shape, depth=1):
+    """True where the closed-form kernels apply: one frame grid for both inputs, whole frames, 'window' / 'linear'."""
+    b, f, k = amp_shape
+    return (tuple(freq_shape) == (b, f, k * depth) and b > 0 and f > 0 and k > 0 and
+            core._on_closed_form_kernels(self.amp_resample_method, f, int(self.n_samples)))
+
+  # -- the reference's interface -----------------------------------------------------
+  def get_controls(self, amplitudes, frequencies):
+    """Network outputs -> {'amplitudes', 'frequencies'} (synths.py:278-301): amp_scale_fn, freq_scale_fn, and - when there is a
+    freq_scale_fn - remove_above_nyquist.  One launch when the class holds the core scale functions itself."""
+    amplitudes, frequencies, flags, depth, hz_min, hz_max = self._prescale(amplitudes, frequencies)
+    core.require_no_grad('Sinusoidal.get_controls (use __call__, which is differentiable)', amplitudes, frequencies)
+    ctl_amp, ctl_freq = self._controls(amplitudes, frequencies, flags, depth, hz_min, hz_max)
+    return {'amplitudes': ctl_amp, 'frequencies': ctl_freq}
+
+  def get_signal(self, amplitudes, frequencies):
+    """Controls -> audio [batch, n_samples] (synths.py:303-323).  Differentiable in both."""
+    amplitudes, frequencies = core.tf_float32(amplitudes), core.tf_float32(frequencies)
+    return self._synthesize(amplitudes, frequencies, 0, 1, 0.0, 0.0, False)[0]
+
+  def call(self, amplitudes, frequencies, return_outputs_dict=False, **kwargs):
+    """get_signal(**get_controls(...)) (processors.py:53-68): the controls kernel, the phase prefix and the synthesis
+    kernel behind one C-ABI call; recorded for torch.autograd when an input requires grad."""
+    for k in ['training', 'mask']:
+      kwargs.pop(k, None)
+    if kwargs:
+      raise TypeError('unexpected keyword arguments: {}'.format(sorted(kwargs)))
+    amplitudes, frequencies, flags, depth, hz_min, hz_max = self._prescale(amplitudes, frequencies)
+    audio, ctl_amp, ctl_freq = self._synthesize(amplitudes, frequencies, flags, depth, hz_min, hz_max, bool(return_outputs_dict))
+    if return_outputs_dict:
+      return dict(signal=audio, controls={'amplitudes': ctl_amp, 'frequencies': ctl_freq})
+    return audio
+
+  # -- synthesis ---------------------------------------------------------------------------
+  def _synthesize(self, amplitudes, frequencies, flags, depth, hz_min, hz_max, want_controls):
+    self._check_3d(amplitudes, frequencies)
+    amplitudes, frequencies = core._broadcast_batch(amplitudes, frequencies)
+    core._check_amp_method(self.amp_resample_method, int(amplitudes.shape[1]), int(self.n_samples))
+    fused = self._on_fused_kernels(amplitudes.shape, frequencies.shape, depth)
+    fn = _SinusoidalFunction if fused else _SinusoidalChainFunction
+    args = (amplitudes, frequencies, self, flags, depth, hz_min, hz_max, want_controls)
+    if core._needs_grad(amplitudes, frequencies):
+      return fn.apply(*args)
+    return fn.forward(core._NoCtx(), *args)
+
+  def _forward_fused(self, amplitudes, frequencies, flags, depth, hz_min, hz_max, want_controls):
+    b, f, k = amplitudes.shape
+    n = int(self.n_samples)
+    lib = _lib.load()
+    dev = amplitudes.device
+    audio = torch.empty((b, n), dtype=torch.float32, device=dev)
+    ws = self._ws.get(core.cached_workspace_bytes('ddsp_sinusoidal_workspace_bytes', b, f, k, n), dev)
+    kflags = flags | self._method_flag()
+    if not flags:
+      rc = lib.ddsp_sinusoidal_signal_f32(amplitudes.data_ptr(), frequencies.data_ptr(), audio.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          b, f, k, n, float(self.sample_rate), kflags, core._stream())
+      _lib.check(rc, 'ddsp_sinusoidal_signal_f32')
+      return audio, amplitudes, frequencies
+    ctl_amp = torch.empty_like(amplitudes) if want_controls else None
+    ctl_freq = torch.empty_like(amplitudes) if want_controls else None
+    rc = lib.ddsp_sinusoidal_f32(amplitudes.data_ptr(), frequencies.data_ptr(), audio.data_ptr(),
+                                 ctl_amp.data_ptr() if want_controls else None, ctl_freq.data_ptr() if want_controls else None,
+                                 ws.data_ptr(), ws.numel(), b, f, k, n, depth, hz_min, hz_max, float(self.sample_rate), kflags,
+                                 core._stream())
+    _lib.check(rc, 'ddsp_sinusoidal_f32')
+    return audio, ctl_amp, ctl_freq
+
+  def _backward_fused(self, amplitudes, frequencies, grad_audio, flags, depth, hz_min, hz_max):
+    b, f, k = amplitudes.shape
+    n = int(self.n_samples)
+    lib = _lib.load()
+    dev = amplitudes.device
+    grad_audio = core.tf_float32(grad_audio)
+    grad_amp, grad_freq = torch.empty_like(amplitudes), torch.empty_like(frequencies)
+    ws = self._ws_bwd.get(core.cached_workspace_bytes('ddsp_sinusoidal_backward_workspace_bytes', b, f, k, n), dev)
+    rc = lib.ddsp_sinusoidal_backward_f32(amplitudes.data_ptr(), frequencies.data_ptr(), grad_audio.data_ptr(), grad_amp.data_ptr(),
+                                          grad_freq.data_ptr(), ws.data_ptr(), ws.numel(), b, f, k, n, depth, hz_min, hz_max,
+                                          float(self.sample_rate), flags | self._method_flag(), core._stream())
+    _lib.check(rc, 'ddsp_sinusoidal_backward_f32')
+    return grad_amp, grad_freq
+
+  def _chain(self, ctl_amp, ctl_freq):
+    """The reference's get_signal op for op on materialised envelopes (synths.py:316-323)."""
+    n = int(self.n_samples)
+    amplitude_envelopes = core.resample(ctl_amp, n, method=self.amp_resample_method)
+    frequency_envelopes = core.resample(ctl_freq, n)
+    if amplitude_envelopes.shape != frequency_envelopes.shape:
+      raise ValueError('amplitudes {} and frequencies {} must have the same batch size and number of sinusoids'.format(
+          tuple(ctl_amp.shape), tuple(ctl_freq.shape)))
+    return core.oscillator_bank(frequency_envelopes, amplitude_envelopes, sample_rate=int(self.sample_rate))
+
+  def _chain_backward(self, ctl_amp, ctl_freq, grad_audio, want_amp, want_freq):
+    """The chain's adjoint op for op: oscillator_bank's two gradients on [B, N, K] envelopes, then resample's adjoint."""
+    lib = _lib.load()
+    b, fa, k = ctl_amp.shape
+    ff = ctl_freq.shape[1]
+    n = int(self.n_samples)
+    dev = ctl_amp.device
+    grad_audio = core.tf_float32(grad_audio)
+    frequency_envelopes = core.resample(ctl_freq, n)
+    ws = self._ws_bwd.get(2 * lib.ddsp_oscillator_bank_workspace_bytes(b, n, k), dev)
+    grad_amp = grad_freq = None
+    if want_amp:
+      grad_env = torch.empty((b, n, k), dtype=torch.float32, device=dev)
+      rc = lib.ddsp_oscillator_bank_grad_amplitudes_f32(frequency_envelopes.data_ptr(), grad_audio.data_ptr(), grad_env.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), b, n, k, int(self.sample_rate), core._stream())
+      _lib.check(rc, 'ddsp_oscillator_bank_grad_amplitudes_f32')
+      grad_amp = torch.empty_like(ctl_amp)
+      rc = lib.ddsp_resample_ex_backward_f32(grad_env.data_ptr(), grad_amp.data_ptr(), b, fa, n, k,
+                                             _lib.RESAMPLE_METHODS[self.amp_resample_method], 1, core._stream())
+      _lib.check(rc, 'ddsp_resample_ex_backward_f32')
+      del grad_env
+    if want_freq:
+      amplitude_envelopes = core.resample(ctl_amp, n, method=self.amp_resample_method)
+      grad_env = torch.empty((b, n, k), dtype=torch.float32, device=dev)
+      rc = lib.ddsp_oscillator_bank_grad_frequencies_f32(frequency_envelopes.data_ptr(), amplitude_envelopes.data_ptr(),
+                                                         grad_audio.data_ptr(), grad_env.data_ptr(), ws.data_ptr(), ws.numel(), b, n, k,
+                                                         int(self.sample_rate), core._stream())
+      _lib.check(rc, 'ddsp_oscillator_bank_grad_frequencies_f32')
+      grad_freq = torch.empty_like(ctl_freq)
+      rc = lib.ddsp_resample_ex_backward_f32(grad_env.data_ptr(), grad_freq.data_ptr(), b, ff, n, k, _lib.RESAMPLE_METHODS['linear'], 1,
+                                             core._stream())
+      _lib.check(rc, 'ddsp_resample_ex_backward_f32')
+    return grad_amp, grad_freq
+
+
+class _SinusoidalFunction(torch.autograd.Function):
+  """torch.autograd node of Sinusoidal on the closed-form kernels (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, amplitudes, frequencies, synth, flags, depth, hz_min, hz_max, want_controls):
+    ctx.save_for_backward(amplitudes, frequencies)
+    ctx.synth, ctx.args = synth, (flags, depth, hz_min, hz_max)
+    audio, ctl_amp, ctl_freq = synth._forward_fused(amplitudes.detach(), frequencies.detach(), flags, depth, hz_min, hz_max,
+                                                    want_controls)
+    if ctl_amp is None:
+      ctl_amp = ctl_freq = amplitudes.new_empty(0)
+    if hasattr(ctx, 'mark_non_differentiable'):
+      ctx.mark_non_differentiable(ctl_amp, ctl_freq)
+    return audio, ctl_amp, ctl_freq
+
+  @staticmethod
+  def backward(ctx, grad_audio, _grad_ctl_amp, _grad_ctl_freq):
+    amplitudes, frequencies = (t.detach() for t in ctx.saved_tensors)
+    grad_amp, grad_freq = ctx.synth._backward_fused(amplitudes, frequencies, grad_audio, *ctx.args)
+    return grad_amp, grad_freq, None, None, None, None, None, None
+
+
+class _SinusoidalChainFunction(torch.autograd.Function):
+  """torch.autograd node of Sinusoidal on the chain of materialised envelopes: the controls kernel, core.resample twice,
+  core.oscillator_bank; backward their adjoints in reverse."""
+
+  @staticmethod
+  def forward(ctx, amplitudes, frequencies, synth, flags, depth, hz_min, hz_max, want_controls):
+    ctx.save_for_backward(amplitudes, frequencies)
+    ctx.synth, ctx.args = synth, (flags, depth, hz_min, hz_max)
+    with torch.no_grad():
+      ctl_amp, ctl_freq = synth._controls(amplitudes.detach(), frequencies.detach(), flags, depth, hz_min, hz_max)
+      audio = synth._chain(ctl_amp, ctl_freq)
+    if flags:
+      if hasattr(ctx, 'mark_non_differentiable'):
+        ctx.mark_non_differentiable(ctl_amp, ctl_freq)
+    else:                                    # (the controls are the inputs themselves: hand back detached views)
+      ctl_amp, ctl_freq = ctl_amp.detach(), ctl_freq.detach()
+    return audio, ctl_amp, ctl_freq
+
+  @staticmethod
+  def backward(ctx, grad_audio, _grad_ctl_amp, _grad_ctl_freq):
+    amplitudes, frequencies = (t.detach() for t in ctx.saved_tensors)
+    flags, depth, hz_min, hz_max = ctx.args
+    synth = ctx.synth
+    want_amp = ctx.needs_input_grad[0] or bool(flags)
+    want_freq = ctx.needs_input_grad[1] or bool(flags)
+    ctl_amp, ctl_freq = synth._controls(amplitudes, frequencies, flags, depth, hz_min, hz_max)
+    grad_ctl_amp, grad_ctl_freq = synth._chain_backward(ctl_amp, ctl_freq, grad_audio, want_amp, want_freq)
+    grad_amp, grad_freq = synth._controls_backward(amplitudes, frequencies, grad_ctl_amp, grad_ctl_freq, flags, depth, hz_min, hz_max)
+    return grad_amp, grad_freq, None, None, None, None, None, None
 
 
 class FilteredNoise(processors.Processor):

@@ -630,6 +630,73 @@ int ddsp_variable_length_delay_backward_f32(const float* phase, const float* aud
                                             void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * synths.Sinusoidal (ddsp/synths.py:260-323) and the frequency scale functions under it (ddsp/core.py:219-348,
+ * 414-507).  Nothing of size [B, N, K] is ever built (csrc/sinusoidal.hip).
+ *
+ * flags:
+ *   DDSP_SIN_AMP_EXP_SIGMOID   amp_scale_fn = core.exp_sigmoid on the amplitudes;
+ *   DDSP_SIN_FREQ_SIGMOID      freq_scale_fn = core.frequencies_sigmoid(depth, hz_min, hz_max), depth <= 64;
+ *   DDSP_SIN_FREQ_SOFTMAX      freq_scale_fn = core.frequencies_softmax(depth, hz_min, hz_max), any depth
+ *                              (both at once: DDSP_ERR_UNSUPPORTED; neither: the frequencies are in Hz, depth is ignored);
+ *   DDSP_SIN_MASK_NYQUIST      core.remove_above_nyquist at frame rate, which Sinusoidal.get_controls applies whenever
+ *                              it has a freq_scale_fn;
+ *   DDSP_SIN_AMP_LINEAR        amp_resample_method 'linear' (default: 'window').
+ *
+ * ddsp_sinusoidal_controls_f32: Sinusoidal.get_controls on `rows` = B * F frames.  amplitudes [rows, K] (NULL together
+ *   with ctl_amplitudes: the frequency scale function on its own), frequencies [rows, K * depth] -> ctl_amplitudes,
+ *   ctl_frequencies [rows, K].  ddsp_sinusoidal_controls_backward_f32 is its adjoint (the Nyquist mask passes no
+ *   gradient to the frequencies; grad_ctl_frequencies may be NULL for zero).
+ * ddsp_sinusoidal_signal_f32: Sinusoidal.get_signal, controls [B,F,K] (Hz) -> audio [B,N].  Scale flags: UNSUPPORTED.
+ * ddsp_sinusoidal_f32: get_signal(**get_controls(...)) from the raw network outputs, amplitudes [B,F,K] and
+ *   frequencies [B,F,K*depth]; ctl_amplitudes / ctl_frequencies [B,F,K]: both NULL, or both out (the controls dict).
+ * ddsp_sinusoidal_backward_f32: grad_audio [B,N] -> grad_amplitudes [B,F,K], grad_frequencies [B,F,K*depth] with respect
+ *   to the inputs the same flags describe (no scale flag: the controls).  No atomics: the same bits on every run and
+ *   for any sub-batch.
+ * All need N % F == 0 (DDSP_ERR_UNSUPPORTED otherwise: the host layer then follows the chain of materialised
+ * envelopes, ddsp_resample_ex_f32 + ddsp_oscillator_bank_f32 and their adjoints).  Any K, any hop.
+ * The frequency envelope is the legacy bilinear resize of the frames (the last one held), the phase the INCLUSIVE
+ * cumulative sum in fp64 cycles, and a sample whose interpolated frequency is >= sample_rate / 2 contributes nothing.
+ */
+#define DDSP_SIN_AMP_EXP_SIGMOID 0x1u
+#define DDSP_SIN_FREQ_SIGMOID 0x2u
+#define DDSP_SIN_FREQ_SOFTMAX 0x4u
+#define DDSP_SIN_MASK_NYQUIST 0x8u
+#define DDSP_SIN_AMP_LINEAR 0x10u
+int ddsp_sinusoidal_controls_f32(const float* amplitudes, const float* frequencies, float* ctl_amplitudes,
+                                 float* ctl_frequencies, size_t rows, int K, int depth, float hz_min, float hz_max,
+                                 float sample_rate, unsigned flags, void* stream);
+int ddsp_sinusoidal_controls_backward_f32(const float* amplitudes, const float* frequencies,
+                                          const float* grad_ctl_amplitudes, const float* grad_ctl_frequencies,
+                                          float* grad_amplitudes, float* grad_frequencies, size_t rows, int K, int depth,
+                                          float hz_min, float hz_max, float sample_rate, unsigned flags, void* stream);
+size_t ddsp_sinusoidal_workspace_bytes(int B, int F, int K, int N);
+int ddsp_sinusoidal_signal_f32(const float* amplitudes, const float* frequencies, float* audio, void* workspace,
+                               size_t workspace_bytes, int B, int F, int K, int N, float sample_rate, unsigned flags,
+                               void* stream);
+int ddsp_sinusoidal_f32(const float* amplitudes, const float* frequencies, float* audio, float* ctl_amplitudes,
+                        float* ctl_frequencies, void* workspace, size_t workspace_bytes, int B, int F, int K, int N,
+                        int depth, float hz_min, float hz_max, float sample_rate, unsigned flags, void* stream);
+size_t ddsp_sinusoidal_backward_workspace_bytes(int B, int F, int K, int N);
+int ddsp_sinusoidal_backward_f32(const float* amplitudes, const float* frequencies, const float* grad_audio,
+                                 float* grad_amplitudes, float* grad_frequencies, void* workspace, size_t workspace_bytes,
+                                 int B, int F, int K, int N, int depth, float hz_min, float hz_max, float sample_rate,
+                                 unsigned flags, void* stream);
+
+/* The elementwise conversions of ddsp/core.py:219-348 on n values:
+ *   MIDI_TO_HZ 440 * 2^((x - 69) / 12) (ZERO_SILENCE: MIDI 0 -> 0 Hz); HZ_TO_MIDI its inverse with x <= 0 -> 0;
+ *   UNIT_TO_MIDI p0 + (p1 - p0) x (CLIP: x clipped to [0, 1] first); MIDI_TO_UNIT (x - p0) / (p1 - p0) (CLIP: the
+ *   result clipped); LOGB log(where(x <= 0, p1, x)) / p0 with p0 the safe log of the base and p1 = eps. */
+#define DDSP_CONVERT_MIDI_TO_HZ 0
+#define DDSP_CONVERT_MIDI_TO_HZ_ZERO_SILENCE 1
+#define DDSP_CONVERT_HZ_TO_MIDI 2
+#define DDSP_CONVERT_UNIT_TO_MIDI 3
+#define DDSP_CONVERT_UNIT_TO_MIDI_CLIP 4
+#define DDSP_CONVERT_MIDI_TO_UNIT 5
+#define DDSP_CONVERT_MIDI_TO_UNIT_CLIP 6
+#define DDSP_CONVERT_LOGB 7
+int ddsp_unit_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
