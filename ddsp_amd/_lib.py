@@ -122,6 +122,20 @@ SIGNATURES = {
     'ddsp_sinusoidal_backward_workspace_bytes': (c_size_t, [c_int] * 4),
     'ddsp_sinusoidal_backward_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t] + [c_int] * 5 + [c_float] * 3 + [c_uint, c_voidp]),
     'ddsp_unit_convert_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_float, c_float, c_voidp]),
+    'ddsp_twm_loss_tensors_f32': (c_int, [c_f32p] * 5 + [c_size_t] + [c_int] * 4 + [c_float] * 3 + [c_voidp]),
+    'ddsp_twm_loss_tensors_backward_f32': (c_int, [c_f32p] * 9 + [c_size_t] + [c_int] * 4 + [c_float] * 3 + [c_voidp]),
+    'ddsp_twm_softmin_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int] + [c_float] * 3 + [c_voidp]),
+    'ddsp_twm_softmin_backward_f32': (c_int, [c_f32p] * 5 + [c_size_t, c_int] + [c_float] * 3 + [c_voidp]),
+    'ddsp_twm_nanargmin_f32': (c_int, [c_f32p] * 4 + [c_voidp, c_size_t, c_int] + [c_float] * 2 + [c_voidp]),
+    'ddsp_kde_nll_f32': (c_int, [c_f32p] * 5 + [c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_kde_nll_backward_f32': (c_int, [c_f32p] * 9 + [c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_sinusoidal_to_harmonic_f32': (c_int, [c_f32p] * 5 + [c_size_t, c_int, c_int, c_float, c_float, c_uint, c_voidp]),
+    'ddsp_sinusoidal_to_harmonic_backward_f32': (c_int, [c_f32p] * 8 + [c_size_t, c_int, c_int, c_float, c_float, c_uint, c_voidp]),
+    'ddsp_mean_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_float, c_voidp]),
+    'ddsp_mean_backward_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_float, c_voidp]),
+    'ddsp_row_mean_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_voidp]),
+    'ddsp_row_mean_backward_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_voidp]),
+    'ddsp_unit_convert_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),
@@ -151,7 +165,11 @@ SIN_MASK_NYQUIST = 0x8
 SIN_AMP_LINEAR = 0x10
 SIN_MAX_SIGMOID_DEPTH = 64
 CONVERT_OPS = {'midi_to_hz': 0, 'midi_to_hz_zero_silence': 1, 'hz_to_midi': 2, 'unit_to_midi': 3, 'unit_to_midi_clip': 4,
-               'midi_to_unit': 5, 'midi_to_unit_clip': 6, 'logb': 7}
+               'midi_to_unit': 5, 'midi_to_unit_clip': 6, 'logb': 7, 'log_floor': 8}
+S2H_NORMALIZE = 0x1
+CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block stages in LDS (csrc/consistency.hip)
+CONSISTENCY_MAX_POINTS = 256
+CONSISTENCY_MAX_GAUSSIANS = 4096
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
 CONV_ADD_DRY = 0x1

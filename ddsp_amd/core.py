@@ -1231,3 +1231,171 @@ def harmonic_to_sinusoidal(harm_amp, harm_dist, f0_hz, sample_rate=16000):
                                                  amps.data_ptr(), b, f, k, _stream())
     _lib.check(rc, 'ddsp_harmonic_envelopes_f32')
   return amps, freqs
+
+
+# --------------------------------------------------------------------------------------
+# sinusoidal_to_harmonic and the differentiable pieces under the consistency losses  (csrc/consistency.hip)
+# --------------------------------------------------------------------------------------
+def _frames3(name, x):
+  if x.dim() != 3:
+    raise ValueError('{} must be [batch, time, n], got shape {}'.format(name, tuple(x.shape)))
+  return x
+
+
+class _SinusoidalToHarmonicFunction(torch.autograd.Function):
+  """torch.autograd node of core.sinusoidal_to_harmonic (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, sin_amps, sin_freqs, f0_hz, args):
+    ctx.save_for_backward(sin_amps, sin_freqs, f0_hz)
+    ctx.args = args
+    b, t, k = sin_amps.shape
+    h = args[0]
+    harm_amp = torch.empty((b, t, 1), dtype=torch.float32, device=sin_amps.device)
+    harm_dist = torch.empty((b, t, h), dtype=torch.float32, device=sin_amps.device)
+    if b * t:
+      rc = _lib.load().ddsp_sinusoidal_to_harmonic_f32(sin_amps.data_ptr(), sin_freqs.data_ptr(), f0_hz.data_ptr(),
+                                                       harm_amp.data_ptr(), harm_dist.data_ptr(), b * t, k, *args, _stream())
+      _lib.check(rc, 'ddsp_sinusoidal_to_harmonic_f32')
+    return harm_amp, harm_dist
+
+  @staticmethod
+  def backward(ctx, grad_amp, grad_dist):
+    sin_amps, sin_freqs, f0_hz = ctx.saved_tensors
+    b, t, k = sin_amps.shape
+    grad_amp, grad_dist = tf_float32(grad_amp), tf_float32(grad_dist)
+    g_amps, g_freqs, g_f0 = torch.empty_like(sin_amps), torch.empty_like(sin_freqs), torch.empty_like(f0_hz)
+    if b * t:
+      rc = _lib.load().ddsp_sinusoidal_to_harmonic_backward_f32(
+          sin_amps.data_ptr(), sin_freqs.data_ptr(), f0_hz.data_ptr(), grad_amp.data_ptr(), grad_dist.data_ptr(),
+          g_amps.data_ptr(), g_freqs.data_ptr(), g_f0.data_ptr(), b * t, k, *ctx.args, _stream())
+      _lib.check(rc, 'ddsp_sinusoidal_to_harmonic_backward_f32')
+    return g_amps, g_freqs, g_f0, None
+
+
+def sinusoidal_to_harmonic(sin_amps, sin_freqs, f0_hz, harmonic_width=0.1, n_harmonics=100, sample_rate=16000,
+                           normalize=False):
+  """core.sinusoidal_to_harmonic (ddsp/core.py:733-781): extract harmonic components from sinusoids given a fundamental.
+
+  sin_amps, sin_freqs [batch, time, n_sinusoids], f0_hz [batch, time, 1] -> (harm_amp [batch, time, 1], harm_dist
+  [batch, time, n_harmonics]).  One kernel per direction, a block per frame: the [batch, time, n_harmonics, n_sinusoids]
+  weights the reference builds five times are never stored.  Differentiable in all three inputs.  Up to 1024 sinusoids
+  and 1024 harmonics."""
+  sin_amps, sin_freqs, f0_hz = tf_float32(sin_amps), tf_float32(sin_freqs), tf_float32(f0_hz)
+  _frames3('sin_amps', sin_amps), _frames3('sin_freqs', sin_freqs), _frames3('f0_hz', f0_hz)
+  if sin_amps.shape != sin_freqs.shape or f0_hz.shape[:2] != sin_amps.shape[:2] or f0_hz.shape[2] != 1:
+    raise ValueError('sin_amps and sin_freqs must be [batch, time, n_sinusoids] and f0_hz [batch, time, 1], got {}, {} and {}'.format(
+        tuple(sin_amps.shape), tuple(sin_freqs.shape), tuple(f0_hz.shape)))
+  k, h = int(sin_amps.shape[2]), int(n_harmonics)
+  if k < 1 or h < 1:
+    raise ValueError('sinusoidal_to_harmonic needs at least one sinusoid and one harmonic, got {} and {}'.format(k, h))
+  if k > _lib.CONSISTENCY_MAX_K or h > _lib.CONSISTENCY_MAX_K:
+    raise NotImplementedError('sinusoidal_to_harmonic takes up to {} sinusoids and harmonics on the MI355X path, got {} and {}'.format(
+        _lib.CONSISTENCY_MAX_K, k, h))
+  args = (h, float(harmonic_width), float(sample_rate), _lib.S2H_NORMALIZE if normalize else 0)
+  if _needs_grad(sin_amps, sin_freqs, f0_hz):
+    return _SinusoidalToHarmonicFunction.apply(sin_amps, sin_freqs, f0_hz, args)
+  return _SinusoidalToHarmonicFunction.forward(_NoCtx(), sin_amps, sin_freqs, f0_hz, args)
+
+
+class _ConvertFunction(torch.autograd.Function):
+  """ddsp_unit_convert_f32 with its adjoint, for the two conversions the consistency losses differentiate through."""
+
+  @staticmethod
+  def forward(ctx, x, op, p0, p1):
+    ctx.save_for_backward(x)
+    ctx.args = (_lib.CONVERT_OPS[op], float(p0), float(p1))
+    out = torch.empty_like(x)
+    if x.numel():
+      rc = _lib.load().ddsp_unit_convert_f32(x.data_ptr(), out.data_ptr(), x.numel(), *ctx.args, _stream())
+      _lib.check(rc, 'ddsp_unit_convert_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    x, = ctx.saved_tensors
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty_like(x)
+    if x.numel():
+      rc = _lib.load().ddsp_unit_convert_backward_f32(x.data_ptr(), grad_out.data_ptr(), grad.data_ptr(), x.numel(), *ctx.args,
+                                                      _stream())
+      _lib.check(rc, 'ddsp_unit_convert_backward_f32')
+    return grad, None, None, None
+
+
+def _convert_diff(op, x, p0=0.0, p1=0.0):
+  x = tf_float32(x)
+  if _needs_grad(x):
+    return _ConvertFunction.apply(x, op, p0, p1)
+  ctx = _NoCtx()
+  return _ConvertFunction.forward(ctx, x, op, p0, p1)
+
+
+def _hz_to_midi_diff(frequencies):
+  """hz_to_midi as losses.freq_loss needs it: differentiable (frequencies <= 0 pass no gradient).  The public
+  core.hz_to_midi keeps refusing tensors that require grad."""
+  return _convert_diff('hz_to_midi', frequencies)
+
+
+def _log10_floor(x, amin):
+  """core.log10(tf.maximum(amin, x)) (ddsp/losses.py:499-502), differentiable: the gradient reaches x where x > amin."""
+  return _convert_diff('log_floor', x, math.log(10.0), amin)
+
+
+class _MeanFunction(torch.autograd.Function):
+  """scale * tf.reduce_mean(x) as a 0-dim tensor: fixed-order fp64 partials (ddsp_mean_f32)."""
+
+  @staticmethod
+  def forward(ctx, x, scale):
+    ctx.shape, ctx.scale = x.shape, float(scale)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    if x.numel() == 0:
+      return out.fill_(float('nan'))
+    rc = _lib.load().ddsp_mean_f32(x.data_ptr(), out.data_ptr(), x.numel(), ctx.scale, _stream())
+    _lib.check(rc, 'ddsp_mean_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    grad_out = tf_float32(grad_out).reshape(1)
+    grad = torch.empty(ctx.shape, dtype=torch.float32, device=grad_out.device)
+    if grad.numel():
+      rc = _lib.load().ddsp_mean_backward_f32(grad_out.data_ptr(), grad.data_ptr(), grad.numel(), ctx.scale, _stream())
+      _lib.check(rc, 'ddsp_mean_backward_f32')
+    return grad, None
+
+
+def _mean(x, scale=1.0):
+  x = tf_float32(x)
+  if _needs_grad(x):
+    return _MeanFunction.apply(x, scale)
+  return _MeanFunction.forward(_NoCtx(), x, scale)
+
+
+class _RowMeanFunction(torch.autograd.Function):
+  """tf.reduce_mean(x, axis=-1) (ddsp_row_mean_f32)."""
+
+  @staticmethod
+  def forward(ctx, x):
+    ctx.shape = x.shape
+    out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    if out.numel():
+      rc = _lib.load().ddsp_row_mean_f32(x.data_ptr(), out.data_ptr(), out.numel(), x.shape[-1], _stream())
+      _lib.check(rc, 'ddsp_row_mean_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty(ctx.shape, dtype=torch.float32, device=grad_out.device)
+    if grad.numel():
+      rc = _lib.load().ddsp_row_mean_backward_f32(grad_out.data_ptr(), grad.data_ptr(), grad_out.numel(), ctx.shape[-1], _stream())
+      _lib.check(rc, 'ddsp_row_mean_backward_f32')
+    return grad
+
+
+def _row_mean(x):
+  x = tf_float32(x)
+  if _needs_grad(x):
+    return _RowMeanFunction.apply(x)
+  return _RowMeanFunction.forward(_NoCtx(), x)

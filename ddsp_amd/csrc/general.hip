@@ -1015,4 +1015,35 @@ DDSP_WEAK size_t ddsp_sinusoidal_backward_workspace_bytes(int, int, int, int) { 
 DDSP_WEAK int ddsp_sinusoidal_backward_f32(const float*, const float*, const float*, float*, float*, void*, size_t, int, int, int, int, int,
                                            float, float, float, unsigned, void*) { return DDSP_ERR_UNSUPPORTED; }
 DDSP_WEAK int ddsp_unit_convert_f32(const float*, float*, size_t, int, float, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+// the same for the entry points of csrc/consistency.hip
+DDSP_WEAK int ddsp_twm_loss_tensors_f32(const float*, const float*, const float*, float*, float*, size_t, int, int, int, int, float, float,
+                                        float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_twm_loss_tensors_backward_f32(const float*, const float*, const float*, const float*, const float*, const float*, float*,
+                                                 float*, float*, size_t, int, int, int, int, float, float, float, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_twm_softmin_f32(const float*, const float*, float*, size_t, int, float, float, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_twm_softmin_backward_f32(const float*, const float*, const float*, float*, float*, size_t, int, float, float, float,
+                                            void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_twm_nanargmin_f32(const float*, const float*, const float*, float*, int*, size_t, int, float, float, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_kde_nll_f32(const float*, const float*, const float*, const float*, float*, size_t, int, int, float, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_kde_nll_backward_f32(const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*,
+                                        size_t, int, int, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinusoidal_to_harmonic_f32(const float*, const float*, const float*, float*, float*, size_t, int, int, float, float,
+                                              unsigned, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinusoidal_to_harmonic_backward_f32(const float*, const float*, const float*, const float*, const float*, float*, float*,
+                                                       float*, size_t, int, int, float, float, unsigned, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_mean_f32(const float*, float*, size_t, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_mean_backward_f32(const float*, float*, size_t, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_row_mean_f32(const float*, float*, size_t, int, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_row_mean_backward_f32(const float*, float*, size_t, int, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_unit_convert_backward_f32(const float*, const float*, float*, size_t, int, float, float, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
 #undef DDSP_WEAK

@@ -192,6 +192,7 @@ __global__ __launch_bounds__(kThreads) void unit_convert_kernel(const float* __r
     case DDSP_CONVERT_UNIT_TO_MIDI_CLIP: y = p0 + (p1 - p0) * fminf(fmaxf(x, 0.0f), 1.0f); break;
     case DDSP_CONVERT_MIDI_TO_UNIT: y = (x - p0) / (p1 - p0); break;
     case DDSP_CONVERT_MIDI_TO_UNIT_CLIP: y = fminf(fmaxf((x - p0) / (p1 - p0), 0.0f), 1.0f); break;
+    case DDSP_CONVERT_LOG_FLOOR: { const float m = fmaxf(p1, x); y = logf(m <= 0.0f ? 1e-5f : m) / p0; break; }   // core.log10(tf.maximum(amin, x)): p0 = ln 10, p1 = amin
     default: y = logf(x <= 0.0f ? p1 : x) / p0; break;                  // DDSP_CONVERT_LOGB: p0 = safe log of the base, p1 = eps
   }
   out[i] = y;
@@ -519,7 +520,7 @@ extern "C" int ddsp_sinusoidal_controls_backward_f32(const float* amplitudes, co
 extern "C" int ddsp_unit_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream) {
   if (!in || !out) return DDSP_ERR_NULL_POINTER;
   if (n == 0 || n > (size_t)0x7fffffff * kThreads) return DDSP_ERR_BAD_SHAPE;
-  if (op < DDSP_CONVERT_MIDI_TO_HZ || op > DDSP_CONVERT_LOGB) return DDSP_ERR_UNSUPPORTED;
+  if (op < DDSP_CONVERT_MIDI_TO_HZ || op > DDSP_CONVERT_LOG_FLOOR) return DDSP_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(unit_convert_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream, in, out, n, op, p0, p1);
   return check_launch();
 }

@@ -472,3 +472,282 @@ class _SpectralLossGeneralFunction(torch.autograd.Function):
   def backward(ctx, grad_loss):
     (grad_audio,) = ctx.saved_tensors
     return None, _scale(grad_audio, grad_loss), None, None
+
+
+# --------------------------------------------------------------------------------------
+# Consistency losses (ddsp/losses.py:489-578, 689-1076).  csrc/consistency.hip holds the kernels of KDEConsistencyLoss, TWMLoss
+# and core.sinusoidal_to_harmonic; the thin ones run on mean_difference.  A loss is a sum of up to three 0-dim terms, each the
+# output of a kernel; the terms are added as 0-dim tensors (as SpectralLoss adds its fused and plain parts).
+# Not built: WassersteinConsistencyLoss / wasserstein_distance, EmbeddingLoss, the CREPE classes.
+# --------------------------------------------------------------------------------------
+def amp_loss(amp, amp_target, loss_type='L1', weights=None, log=False, amin=1e-5):
+  """Loss comparing two amplitudes (scale logarithmically) (ddsp/losses.py:492-504)."""
+  if log:
+    amp = core._log10_floor(amp, amin)
+    amp_target = core._log10_floor(amp_target, amin)
+  return mean_difference(amp, amp_target, loss_type, weights)
+
+
+def freq_loss(f_hz, f_hz_target, loss_type='L1', weights=None):
+  """Loss comparing two frequencies, in MIDI (ddsp/losses.py:507-513)."""
+  f_midi = core._hz_to_midi_diff(f_hz)
+  f_midi_target = core._hz_to_midi_diff(f_hz_target)
+  return mean_difference(f_midi, f_midi_target, loss_type, weights)
+
+
+def _weighted(weight, loss):
+  """weight * loss for a 0-dim loss, on ddsp_mean_f32 (the mean of one element, scaled)."""
+  return core._mean(loss.reshape(1), float(weight))
+
+
+class FilteredNoiseConsistencyLoss(Loss):
+  """Consistency loss for synthesizer controls (ddsp/losses.py:516-530)."""
+
+  def __init__(self, weight=1.0, name='filtered_noise_consistency_loss'):
+    super().__init__(name=name)
+    self.weight = weight
+
+  def call(self, noise_magnitudes, noise_magnitudes_target):
+    return _weighted(self.weight, amp_loss(noise_magnitudes, noise_magnitudes_target))
+
+
+class HarmonicConsistencyLoss(Loss):
+  """Consistency loss for synthesizer controls (ddsp/losses.py:533-578): a dictionary of three weighted terms."""
+
+  def __init__(self, amp_weight=1.0, dist_weight=1.0, f0_weight=1.0, amp_threshold=1e-4, name='harmonic_consistency_loss'):
+    super().__init__(name=name)
+    self.amp_weight = amp_weight
+    self.dist_weight = dist_weight
+    self.f0_weight = f0_weight
+    self.amp_threshold = amp_threshold
+
+  def call(self, harm_amp, harm_amp_target, harm_dist, harm_dist_target, f0_hz, f0_hz_target):
+    losses_dict = {}
+    # mask where the target is below the threshold amplitude: a comparison, not differentiable - a weight
+    target = core.tf_float32(harm_amp_target).detach()
+    threshold = torch.full((1,), float(self.amp_threshold), dtype=torch.float32, device=target.device)
+    weights = core.tf_float32(target >= threshold)
+    losses_dict['harm_amp_loss'] = _weighted(self.amp_weight, amp_loss(harm_amp, harm_amp_target))
+    losses_dict['harm_dist_loss'] = _weighted(self.dist_weight, amp_loss(harm_dist, harm_dist_target, weights=weights))
+    losses_dict['f0_hz_loss'] = _weighted(self.f0_weight, freq_loss(f0_hz, f0_hz_target, weights=weights))
+    return losses_dict
+
+  def get_losses_dict(self, *args, **kwargs):
+    return self(*args, **kwargs)
+
+
+class ParamLoss(Loss):
+  """Loss on the mean difference between any two tensors (ddsp/losses.py:1064-1076)."""
+
+  def __init__(self, weight=1.0, loss_type='L1', name='param_loss'):
+    super().__init__(name=name)
+    self.weight = weight
+    self.loss_type = loss_type
+
+  def call(self, pred, target, weights=None):
+    return _weighted(self.weight, mean_difference(pred, target, self.loss_type, weights))
+
+
+def _sinusoid_frames(names, tensors, same_last=True):
+  """[batch, time, n] tensors that share batch and time (and the last axis, if same_last) -> contiguous fp32."""
+  out = [core.tf_float32(t) for t in tensors]
+  shapes = ', '.join('{} {}'.format(n, tuple(t.shape)) for n, t in zip(names, out))
+  if any(t.dim() != 3 for t in out) or any(t.shape[:2] != out[0].shape[:2] for t in out):
+    raise ValueError('expected [batch, time, n] tensors with equal batch and time, got ' + shapes)
+  if same_last and any(t.shape[2] != out[0].shape[2] for t in out):
+    raise ValueError('the last axes must be equal, got ' + shapes)
+  if any(t.shape[2] < 1 for t in out):
+    raise ValueError('the last axes must not be empty, got ' + shapes)
+  return out
+
+
+class _KdeNllFunction(torch.autograd.Function):
+  """torch.autograd node of KDEConsistencyLoss.nll (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, amps, freqs, amps_target, freqs_target, scale):
+    ctx.save_for_backward(amps, freqs, amps_target, freqs_target)
+    ctx.scale = scale
+    b, t, k = amps.shape
+    nll = torch.empty((b, t), dtype=torch.float32, device=amps.device)
+    if b * t:
+      rc = _lib.load().ddsp_kde_nll_f32(amps.data_ptr(), freqs.data_ptr(), amps_target.data_ptr(), freqs_target.data_ptr(),
+                                        nll.data_ptr(), b * t, k, amps_target.shape[2], scale, core._stream())
+      _lib.check(rc, 'ddsp_kde_nll_f32')
+    return nll
+
+  @staticmethod
+  def backward(ctx, grad_nll):
+    amps, freqs, amps_target, freqs_target = ctx.saved_tensors
+    b, t, k = amps.shape
+    grad_nll = core.tf_float32(grad_nll)
+    grads = [torch.empty_like(x) for x in (amps, freqs, amps_target, freqs_target)]
+    if b * t:
+      rc = _lib.load().ddsp_kde_nll_backward_f32(amps.data_ptr(), freqs.data_ptr(), amps_target.data_ptr(), freqs_target.data_ptr(),
+                                                 grad_nll.data_ptr(), *[g.data_ptr() for g in grads], b * t, k,
+                                                 amps_target.shape[2], ctx.scale, core._stream())
+      _lib.check(rc, 'ddsp_kde_nll_backward_f32')
+    return grads[0], grads[1], grads[2], grads[3], None
+
+
+class KDEConsistencyLoss(Loss):
+  """Compare similarity of two traces of sinusoids using kernels (ddsp/losses.py:689-813): a Gaussian kernel density estimate
+  in both directions, in MIDI, and the difference of the mean amplitudes.  The [batch, time, K, K] tensors of the reference
+  are never built (csrc/consistency.hip: a block per frame); up to 1024 sinusoids on either side."""
+
+  def __init__(self, weight_a=1.0, weight_b=1.0, weight_mean_amp=1.0, scale_a=0.1, scale_b=0.1, name='kde_consistency_loss'):
+    super().__init__(name=name)
+    self.weight_a = weight_a
+    self.weight_b = weight_b
+    self.weight_mean_amp = weight_mean_amp
+    self.scale_a = scale_a
+    self.scale_b = scale_b
+
+  def call(self, amps_a, freqs_a, amps_b, freqs_b):
+    """Scalar, weighted -log p(a|b) - log p(b|a) (+ the mean-amplitude term).  A term whose weight is not > 0 is skipped."""
+    amps_a, freqs_a = _sinusoid_frames(('amps_a', 'freqs_a'), (amps_a, freqs_a))
+    amps_b, freqs_b = _sinusoid_frames(('amps_b', 'freqs_b'), (amps_b, freqs_b))
+    loss = 0.0
+    if self.weight_a > 0.0:
+      loss = loss + core._mean(self.nll(amps_a, freqs_a, amps_b, freqs_b, self.scale_b), self.weight_a)
+    if self.weight_b > 0.0:
+      loss = loss + core._mean(self.nll(amps_b, freqs_b, amps_a, freqs_a, self.scale_a), self.weight_b)
+    if self.weight_mean_amp > 0.0:
+      loss = loss + _weighted(self.weight_mean_amp, mean_difference(core._row_mean(amps_a), core._row_mean(amps_b), 'L1'))
+    return loss
+
+  def nll(self, amps, freqs, amps_target, freqs_target, scale_target):
+    """-log p(source | target), [batch, time]."""
+    amps, freqs = _sinusoid_frames(('amps', 'freqs'), (amps, freqs))
+    amps_target, freqs_target = _sinusoid_frames(('amps_target', 'freqs_target'), (amps_target, freqs_target))
+    _sinusoid_frames(('amps', 'amps_target'), (amps, amps_target), same_last=False)
+    if max(amps.shape[2], amps_target.shape[2]) > _lib.CONSISTENCY_MAX_K:
+      raise NotImplementedError('KDEConsistencyLoss takes up to {} sinusoids on the MI355X path, got {} and {}'.format(
+          _lib.CONSISTENCY_MAX_K, amps.shape[2], amps_target.shape[2]))
+    args = (amps, freqs, amps_target, freqs_target, float(scale_target))
+    if core._needs_grad(*args[:4]):
+      return _KdeNllFunction.apply(*args)
+    return _KdeNllFunction.forward(core._NoCtx(), *args)
+
+
+class _TwmTensorsFunction(torch.autograd.Function):
+  """torch.autograd node of TWMLoss.get_loss_tensors (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, f0_candidates, freqs, amps, args):
+    b, t, c = f0_candidates.shape
+    sin_loss = torch.empty((b, t, c), dtype=torch.float32, device=freqs.device)
+    harm_loss = torch.empty_like(sin_loss)
+    if b * t:
+      rc = _lib.load().ddsp_twm_loss_tensors_f32(f0_candidates.data_ptr(), freqs.data_ptr(), amps.data_ptr(), sin_loss.data_ptr(),
+                                                 harm_loss.data_ptr(), b * t, c, freqs.shape[2], *args, core._stream())
+      _lib.check(rc, 'ddsp_twm_loss_tensors_f32')
+    ctx.save_for_backward(f0_candidates, freqs, amps, sin_loss)
+    ctx.args = args
+    return sin_loss, harm_loss
+
+  @staticmethod
+  def backward(ctx, grad_sin, grad_harm):
+    f0_candidates, freqs, amps, sin_loss = ctx.saved_tensors
+    b, t, c = f0_candidates.shape
+    grad_sin, grad_harm = core.tf_float32(grad_sin), core.tf_float32(grad_harm)
+    grads = [torch.empty_like(x) for x in (f0_candidates, freqs, amps)]
+    if b * t:
+      rc = _lib.load().ddsp_twm_loss_tensors_backward_f32(
+          f0_candidates.data_ptr(), freqs.data_ptr(), amps.data_ptr(), sin_loss.data_ptr(), grad_sin.data_ptr(), grad_harm.data_ptr(),
+          *[g.data_ptr() for g in grads], b * t, c, freqs.shape[2], *ctx.args, core._stream())
+      _lib.check(rc, 'ddsp_twm_loss_tensors_backward_f32')
+    return grads[0], grads[1], grads[2], None
+
+
+class _TwmSoftminFunction(torch.autograd.Function):
+  """Per frame sum_c L_c softmax(-L / temperature)_c, L = w_s S + w_h H (ddsp/losses.py:917-920)."""
+
+  @staticmethod
+  def forward(ctx, sin_loss, harm_loss, args):
+    ctx.save_for_backward(sin_loss, harm_loss)
+    ctx.args = args
+    b, t, c = sin_loss.shape
+    out = torch.empty((b, t), dtype=torch.float32, device=sin_loss.device)
+    if b * t:
+      rc = _lib.load().ddsp_twm_softmin_f32(sin_loss.data_ptr(), harm_loss.data_ptr(), out.data_ptr(), b * t, c, *args, core._stream())
+      _lib.check(rc, 'ddsp_twm_softmin_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    sin_loss, harm_loss = ctx.saved_tensors
+    b, t, c = sin_loss.shape
+    grad_out = core.tf_float32(grad_out)
+    g_sin, g_harm = torch.empty_like(sin_loss), torch.empty_like(harm_loss)
+    if b * t:
+      rc = _lib.load().ddsp_twm_softmin_backward_f32(sin_loss.data_ptr(), harm_loss.data_ptr(), grad_out.data_ptr(), g_sin.data_ptr(),
+                                                     g_harm.data_ptr(), b * t, c, *ctx.args, core._stream())
+      _lib.check(rc, 'ddsp_twm_softmin_backward_f32')
+    return g_sin, g_harm, None
+
+
+class TWMLoss(Loss):
+  """Two-way Mismatch, encourages sinusoids to be harmonics of the best f0 candidate (ddsp/losses.py:819-1061).
+
+  Loss = -log p(sinusoids | harmonics) - log p(harmonics | sinusoids) per candidate, a softmin over the candidates.  The
+  [batch, time, candidates, sinusoids, gaussians] and [batch, time, candidates, points, sinusoids] tensors of the reference are
+  never built (csrc/consistency.hip: a block per frame).  Up to 1024 sinusoids, 256 harmonic points, 4096 harmonic
+  Gaussians, any number of candidates."""
+
+  def __init__(self, sinusoids_weight=1.0, harmonics_weight=1.0, sinusoids_scale=0.5, harmonics_scale=0.2, n_harmonic_points=10,
+               n_harmonic_gaussians=30, softmin_temperature=1.0, sample_rate=16000, name='twm_loss'):
+    super().__init__(name=name)
+    self.softmin_temperature = softmin_temperature
+    self.sample_rate = sample_rate
+    self.sinusoids_weight = sinusoids_weight
+    self.harmonics_weight = harmonics_weight
+    self.sinusoids_scale = sinusoids_scale
+    self.n_harmonic_points = n_harmonic_points
+    self.harmonics_scale = harmonics_scale
+    self.n_harmonic_gaussians = n_harmonic_gaussians
+
+  def call(self, f0_candidates, freqs, amps):
+    """Scalar: the mean over [batch, time, candidates] of L softmax(-L / temperature), L the weighted sum of the two tensors."""
+    sinusoids_loss, harmonics_loss = self.get_loss_tensors(f0_candidates, freqs, amps)
+    args = (sinusoids_loss, harmonics_loss,
+            (float(self.sinusoids_weight), float(self.harmonics_weight), float(self.softmin_temperature)))
+    if core._needs_grad(sinusoids_loss, harmonics_loss):
+      frame_loss = _TwmSoftminFunction.apply(*args)
+    else:
+      frame_loss = _TwmSoftminFunction.forward(core._NoCtx(), *args)
+    return core._mean(frame_loss, 1.0 / sinusoids_loss.shape[2])
+
+  def predict_f0(self, f0_candidates, freqs, amps):
+    """The most likely f0 among the candidates at each timestep: numpy array [batch, time, 1].  The arg-min runs on the
+    device and ignores NaN (np.nanargmin); a frame whose losses are all NaN raises ValueError, as numpy does."""
+    with torch.no_grad():
+      sinusoids_loss, harmonics_loss = self.get_loss_tensors(f0_candidates, freqs, amps)
+      f0_candidates = core.tf_float32(f0_candidates)
+      b, t, c = sinusoids_loss.shape
+      f0_hz = torch.empty((b, t, 1), dtype=torch.float32, device=sinusoids_loss.device)
+      flag = torch.zeros((1,), dtype=torch.int32, device=sinusoids_loss.device)
+      if b * t:
+        rc = _lib.load().ddsp_twm_nanargmin_f32(sinusoids_loss.data_ptr(), harmonics_loss.data_ptr(), f0_candidates.data_ptr(),
+                                                f0_hz.data_ptr(), flag.data_ptr(), b * t, c, float(self.sinusoids_weight),
+                                                float(self.harmonics_weight), core._stream())
+        _lib.check(rc, 'ddsp_twm_nanargmin_f32')
+      if int(flag.cpu()[0]):
+        raise ValueError('All-NaN slice encountered')
+      return f0_hz.cpu().numpy()
+
+  def get_loss_tensors(self, f0_candidates, freqs, amps):
+    """(-log p(sinusoids | harmonics), -log p(harmonics | sinusoids)), both [batch, time, f0_candidate]."""
+    freqs, amps = _sinusoid_frames(('freqs', 'amps'), (freqs, amps))
+    f0_candidates, _ = _sinusoid_frames(('f0_candidates', 'freqs'), (f0_candidates, freqs), same_last=False)
+    p, g = int(self.n_harmonic_points), int(self.n_harmonic_gaussians)
+    if p < 1 or g < 1:
+      raise ValueError('n_harmonic_points and n_harmonic_gaussians must be at least 1, got {} and {}'.format(p, g))
+    if freqs.shape[2] > _lib.CONSISTENCY_MAX_K or p > _lib.CONSISTENCY_MAX_POINTS or g > _lib.CONSISTENCY_MAX_GAUSSIANS:
+      raise NotImplementedError('TWMLoss takes up to {} sinusoids, {} harmonic points and {} harmonic gaussians on the MI355X path, '
+                                'got {}, {} and {}'.format(_lib.CONSISTENCY_MAX_K, _lib.CONSISTENCY_MAX_POINTS,
+                                                           _lib.CONSISTENCY_MAX_GAUSSIANS, freqs.shape[2], p, g))
+    args = (p, g, float(self.sinusoids_scale), float(self.harmonics_scale), float(self.sample_rate))
+    if core._needs_grad(f0_candidates, freqs, amps):
+      return _TwmTensorsFunction.apply(f0_candidates, freqs, amps, args)
+    return _TwmTensorsFunction.forward(core._NoCtx(), f0_candidates, freqs, amps, args)

@@ -697,6 +697,68 @@ int ddsp_sinusoidal_backward_f32(const float* amplitudes, const float* frequenci
 int ddsp_unit_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The sinusoidal consistency losses (ddsp/losses.py:689-1061) and core.sinusoidal_to_harmonic (ddsp/core.py:733-781):
+ * csrc/consistency.hip.  `rows` = B * T frames; a block owns a frame, nothing of size [rows, C, K], [rows, K, K] or
+ * [rows, H, K] is built, forward or backward, and no call needs a workspace.  No atomics: the same bits on every run and
+ * for any subset of the rows.  Bounds (DDSP_ERR_UNSUPPORTED beyond): K, K_target, H <= 1024; n_harmonic_points <= 256;
+ * n_harmonic_gaussians <= 4096; any C.
+ *
+ * ddsp_twm_loss_tensors_f32: TWMLoss.get_loss_tensors.  f0_candidates [rows, C], freqs / amps [rows, K] ->
+ *   sinusoids_loss, harmonics_loss [rows, C].  _backward_: the two incoming gradients [rows, C] and the forward's
+ *   sinusoids_loss -> grad_f0_candidates [rows, C], grad_freqs, grad_amps [rows, K].
+ * ddsp_twm_softmin_f32: per frame sum_c L_c softmax(-L / temperature)_c with L = w_s S + w_h H -> frame_loss [rows]
+ *   (TWMLoss.call is its mean divided by C); _backward_ its adjoint.
+ * ddsp_twm_nanargmin_f32: TWMLoss.predict_f0: the candidate of the smallest L that is not NaN -> f0_hz [rows];
+ *   *all_nan_flag (zeroed by the caller) is set to 1 if some frame has no such candidate.
+ * ddsp_kde_nll_f32: KDEConsistencyLoss.nll, source amps / freqs [rows, K], target [rows, K_target] -> nll [rows];
+ *   _backward_: grad_nll [rows] -> the four gradients.
+ * ddsp_sinusoidal_to_harmonic_f32: sin_amps / sin_freqs [rows, K], f0_hz [rows] -> harm_amp [rows], harm_dist [rows, H];
+ *   flags: DDSP_S2H_NORMALIZE.  _backward_: grad_harm_amp [rows], grad_harm_dist [rows, H] -> the three gradients.
+ * ddsp_mean_f32: out[0] = scale * mean(x[0 .. n)) in fixed-order fp64 partials; _backward_: grad_x[i] = grad_out[0] scale / n.
+ * ddsp_row_mean_f32: tf.reduce_mean(x, axis=-1), [rows, K] -> [rows]; _backward_ its adjoint.
+ * ddsp_unit_convert_backward_f32: grad_in = grad_out * d op(in) / d in for DDSP_CONVERT_HZ_TO_MIDI and
+ *   DDSP_CONVERT_LOG_FLOOR (log10(max(p1, x)), p0 = ln 10: losses.amp_loss(log=True)).
+ */
+#define DDSP_S2H_NORMALIZE 0x1u
+#define DDSP_CONVERT_LOG_FLOOR 8
+int ddsp_twm_loss_tensors_f32(const float* f0_candidates, const float* freqs, const float* amps, float* sinusoids_loss,
+                              float* harmonics_loss, size_t rows, int C, int K, int n_harmonic_points,
+                              int n_harmonic_gaussians, float sinusoids_scale, float harmonics_scale, float sample_rate,
+                              void* stream);
+int ddsp_twm_loss_tensors_backward_f32(const float* f0_candidates, const float* freqs, const float* amps,
+                                       const float* sinusoids_loss, const float* grad_sinusoids_loss,
+                                       const float* grad_harmonics_loss, float* grad_f0_candidates, float* grad_freqs,
+                                       float* grad_amps, size_t rows, int C, int K, int n_harmonic_points,
+                                       int n_harmonic_gaussians, float sinusoids_scale, float harmonics_scale,
+                                       float sample_rate, void* stream);
+int ddsp_twm_softmin_f32(const float* sinusoids_loss, const float* harmonics_loss, float* frame_loss, size_t rows, int C,
+                         float sinusoids_weight, float harmonics_weight, float temperature, void* stream);
+int ddsp_twm_softmin_backward_f32(const float* sinusoids_loss, const float* harmonics_loss, const float* grad_frame_loss,
+                                  float* grad_sinusoids_loss, float* grad_harmonics_loss, size_t rows, int C,
+                                  float sinusoids_weight, float harmonics_weight, float temperature, void* stream);
+int ddsp_twm_nanargmin_f32(const float* sinusoids_loss, const float* harmonics_loss, const float* f0_candidates, float* f0_hz,
+                           int* all_nan_flag, size_t rows, int C, float sinusoids_weight, float harmonics_weight,
+                           void* stream);
+int ddsp_kde_nll_f32(const float* amps, const float* freqs, const float* amps_target, const float* freqs_target, float* nll,
+                     size_t rows, int K, int K_target, float scale_target, void* stream);
+int ddsp_kde_nll_backward_f32(const float* amps, const float* freqs, const float* amps_target, const float* freqs_target,
+                              const float* grad_nll, float* grad_amps, float* grad_freqs, float* grad_amps_target,
+                              float* grad_freqs_target, size_t rows, int K, int K_target, float scale_target, void* stream);
+int ddsp_sinusoidal_to_harmonic_f32(const float* sin_amps, const float* sin_freqs, const float* f0_hz, float* harm_amp,
+                                    float* harm_dist, size_t rows, int K, int H, float harmonic_width, float sample_rate,
+                                    unsigned flags, void* stream);
+int ddsp_sinusoidal_to_harmonic_backward_f32(const float* sin_amps, const float* sin_freqs, const float* f0_hz,
+                                             const float* grad_harm_amp, const float* grad_harm_dist, float* grad_sin_amps,
+                                             float* grad_sin_freqs, float* grad_f0_hz, size_t rows, int K, int H,
+                                             float harmonic_width, float sample_rate, unsigned flags, void* stream);
+int ddsp_mean_f32(const float* x, float* out, size_t n, float scale, void* stream);
+int ddsp_mean_backward_f32(const float* grad_out, float* grad_x, size_t n, float scale, void* stream);
+int ddsp_row_mean_f32(const float* x, float* out, size_t rows, int K, void* stream);
+int ddsp_row_mean_backward_f32(const float* grad_out, float* grad_x, size_t rows, int K, void* stream);
+int ddsp_unit_convert_backward_f32(const float* in, const float* grad_out, float* grad_in, size_t n, int op, float p0,
+                                   float p1, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
