@@ -66,6 +66,9 @@ SIGNATURES = {
     'ddsp_stft_frames_f32': (c_int, [c_f32p] * 2 + [c_int] * 7 + [c_voidp]),
     'ddsp_stft_frames_mag_ex_f32': (c_int, [c_f32p] * 2 + [c_int] * 7 + [c_voidp]),
     'ddsp_stft_frames_mag_backward_f32': (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_voidp]),
+    'ddsp_mel_features_f32': (c_int, [c_f32p] * 5 + [c_int] * 11 + [c_float, c_voidp]),
+    'ddsp_frame_energy_f32': (c_int, [c_f32p] * 2 + [c_int] * 6 + [c_float] * 2 + [c_uint, c_voidp]),
+    'ddsp_db_convert_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_loudness_from_mag_f32': (c_int, [c_f32p] * 3 + [c_int] * 3 + [ctypes.c_float] * 2 + [c_voidp]),
     'ddsp_loudness_from_mag_backward_f32': (c_int, [c_f32p] * 4 + [c_int] * 3 + [ctypes.c_float] * 2 + [c_voidp]),
     'ddsp_uniform_noise_f32': (c_int, [c_f32p, c_int, c_int, c_u64, c_u64, c_voidp]),
@@ -166,6 +169,9 @@ SIN_AMP_LINEAR = 0x10
 SIN_MAX_SIGMOID_DEPTH = 64
 CONVERT_OPS = {'midi_to_hz': 0, 'midi_to_hz_zero_silence': 1, 'hz_to_midi': 2, 'unit_to_midi': 3, 'unit_to_midi_clip': 4,
                'midi_to_unit': 5, 'midi_to_unit_clip': 6, 'logb': 7, 'log_floor': 8}
+DB_OPS = {'power_to_db': 0, 'amplitude_to_db': 1, 'db_to_power': 2, 'db_to_amplitude': 3}
+MEL_MODES = {'mel': 0, 'logmel': 1, 'mfcc': 2}
+ENERGY_DB = 0x1
 S2H_NORMALIZE = 0x1
 CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block stages in LDS (csrc/consistency.hip)
 CONSISTENCY_MAX_POINTS = 256

@@ -1134,6 +1134,42 @@ def midi_to_unit(midi, midi_min=20.0, midi_max=90.0, clip=False):
   return _convert('midi_to_unit_clip' if clip else 'midi_to_unit', midi, midi_min, midi_max)
 
 
+DB_RANGE = 80.0
+
+
+def _convert_db(op, x, p0=0.0, p1=0.0):
+  x = tf_float32(x).contiguous()
+  require_no_grad('core.' + op, x)
+  out = torch.empty_like(x)
+  if x.numel():
+    rc = _lib.load().ddsp_db_convert_f32(x.data_ptr(), out.data_ptr(), x.numel(), _lib.DB_OPS[op], float(p0), float(p1), _stream())
+    _lib.check(rc, 'ddsp_db_convert_f32')
+  return out
+
+
+def power_to_db(power, ref_db=0.0, range_db=DB_RANGE, use_tf=True):
+  """core.power_to_db (ddsp/core.py:253-267): max(10 log10(max(10^(-range_db / 10), power)) - ref_db, -range_db).  `use_tf` is
+  accepted and ignored (one implementation)."""
+  del use_tf
+  return _convert_db('power_to_db', power, ref_db, range_db)
+
+
+def amplitude_to_db(amplitude, ref_db=0.0, range_db=DB_RANGE, use_tf=True):
+  """core.amplitude_to_db (ddsp/core.py:247-250): power_to_db of amplitude^2."""
+  del use_tf
+  return _convert_db('amplitude_to_db', amplitude, ref_db, range_db)
+
+
+def db_to_power(db):
+  """core.db_to_power (ddsp/core.py:275-277): 10^(db / 10)."""
+  return _convert_db('db_to_power', db)
+
+
+def db_to_amplitude(db):
+  """core.db_to_amplitude (ddsp/core.py:270-272): db_to_power(db / 2)."""
+  return _convert_db('db_to_amplitude', db)
+
+
 def unit_to_hz(unit, hz_min, hz_max, clip=False):
   """core.unit_to_hz (ddsp/core.py:327-336): [0, 1] to [hz_min, hz_max] on a logarithmic scale (the bounds are numbers)."""
   return midi_to_hz(unit_to_midi(unit, _hz_to_midi_number(hz_min), _hz_to_midi_number(hz_max), clip))

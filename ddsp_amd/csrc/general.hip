@@ -1046,4 +1046,9 @@ DDSP_WEAK int ddsp_row_mean_backward_f32(const float*, float*, size_t, int, void
 DDSP_WEAK int ddsp_unit_convert_backward_f32(const float*, const float*, float*, size_t, int, float, float, void*) {
   return DDSP_ERR_UNSUPPORTED;
 }
+// and of csrc/features.hip
+DDSP_WEAK int ddsp_frame_energy_f32(const float*, float*, int, int, int, int, int, int, float, float, unsigned, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_db_convert_f32(const float*, float*, size_t, int, float, float, void*) { return DDSP_ERR_UNSUPPORTED; }
 #undef DDSP_WEAK

@@ -1045,6 +1045,82 @@ __global__ __launch_bounds__(kSlThreads) void stft_tq_mag_kernel(const float* __
   }
 }
 
+// ---- spectral_ops.compute_mel / compute_logmel / compute_mfcc (ddsp/spectral_ops.py:73-133) on the block of stft_tq_mag_kernel ----
+// The magnitudes of the block's G frames stay in LDS (G (H + 1) floats beside the transform's array); the
+// [B, frames, S / 2 + 1] tensor of compute_mag is never written.  tf.signal.linear_to_mel_weight_matrix is banded: the weights
+// of band m cover ONE run of bins, start[m] .. start[m] + count[m] - 1, and a bin feeds at most two bands, so a thread takes one
+// (frame, band) pair and walks its run in bin order - 2 (H + 1) products per frame where the dense product has bins (H + 1).
+// The [G][bins] tile of mel values (or their safe logs) takes the place of the transform's array, which nobody reads any
+// more; MFCC: a thread per (frame, coefficient) walks the tile in band order against the DCT table, transposed by the caller
+// ([bins][mfcc_bins]: neighbouring lanes read neighbouring words).  Both sums are fp64 FMAs in a fixed order: no atomics, the
+// same bits for a row alone and in a batch.  An empty band (count 0: narrower than a bin) sums to exactly 0.
+struct SlMelArgs {
+  const int* __restrict__ bands;         // [3][bins]: start, count, first packed weight
+  const float* __restrict__ weights;     // the bands' non-zero weights, packed band after band
+  const float* __restrict__ dct_t;       // [bins][mfcc_bins] (mode 2)
+  int bins, mfcc_bins, n_weights, mode;  // mode 0: mel, 1: safe_log(mel), 2: MFCC
+  float eps;
+};
+
+template <int S>
+__global__ __launch_bounds__(kSlThreads) void stft_tq_mel_kernel(const float* __restrict__ audio, float* __restrict__ out, int N,
+                                                                 int n_frames, SlFrameGeom fg, SlMelArgs p) {
+  constexpr int H = S / 2, G = kSlPoints / H, LOG2G = __builtin_ctz(G);
+  static_assert(kSlStore * 8 + G * (H + 1) * 4 <= 65536, "the transform's array and the magnitudes share 64 KB of LDS");
+  __shared__ __attribute__((aligned(16))) float2 s[kSlStore];
+  __shared__ float m[G * (H + 1)];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int f0 = blockIdx.x * G;
+  tq_load_frames<S>(s, audio + (size_t)b * N, tid, f0, G, n_frames, N, fg);
+  __syncthreads();
+  sl_forward<H>(s, tid, G, 0);
+  __syncthreads();
+  for (int e = tid; e < G * (H + 1); e += kSlThreads) {         // (frames past the last one were loaded as zeros)
+    const int g = e / (H + 1), k = e - g * (H + 1);
+    const int ia = sl_pos<H>(k & (H - 1)), ib = sl_pos<H>((H - k) & (H - 1));
+    const float rev = (float)k * (1.0f / (float)S);
+    const float c = __builtin_amdgcn_cosf(rev), sn = __builtin_amdgcn_sinf(rev);
+    const float2 za = s[SP(g * H + ia)], zb = s[SP(g * H + ib)];
+    const float ex = 0.5f * (za.x + zb.x), ey = 0.5f * (za.y - zb.y);       // as stft_tq_mag_kernel
+    const float ox = 0.5f * (za.y + zb.y), oy = -0.5f * (za.x - zb.x);
+    const float xr = ex + fmaf(ox, c, oy * sn), xi = ey + fmaf(oy, c, -ox * sn);
+    m[e] = sl_sqrt(fmaf(xr, xr, xi * xi));
+  }
+  __syncthreads();
+  float* __restrict__ tile = reinterpret_cast<float*>(s);       // [G][bins], G bins <= 2 kSlPoints (checked at launch)
+  const int bins = p.bins;
+  for (int it = tid; it < G * bins; it += kSlThreads) {          // neighbouring lanes: one band, G frames (rows H + 1 apart)
+    const int g = it & (G - 1), band = it >> LOG2G;
+    const int k0 = p.bands[band], off = p.bands[2 * bins + band];
+    int cnt = p.bands[bins + band];
+    if (k0 < 0 || cnt < 0 || k0 + cnt > H + 1 || off < 0 || off + cnt > p.n_weights) cnt = 0;
+    const float* __restrict__ w = p.weights + off;
+    const float* __restrict__ mg = m + g * (H + 1) + k0;
+    double acc = 0.0;
+    for (int j = 0; j < cnt; ++j) acc = fma((double)mg[j], (double)w[j], acc);
+    float v = (float)acc;
+    if (p.mode) v = logf(v <= 0.0f ? p.eps : v);                 // core.safe_log
+    tile[g * bins + band] = v;
+  }
+  __syncthreads();
+  const int live = min(G, n_frames - f0);
+  if (p.mode < 2) {
+    float* __restrict__ dst = out + ((size_t)b * n_frames + f0) * bins;      // the block's frames are one run of the output
+    for (int it = tid; it < live * bins; it += kSlThreads) dst[it] = tile[it];
+    return;
+  }
+  // tf.signal.mfccs_from_log_mel_spectrograms, the first mfcc_bins rows of the scaled DCT-II
+  const int nc = p.mfcc_bins;
+  float* __restrict__ dst = out + ((size_t)b * n_frames + f0) * nc;
+  for (int it = tid; it < live * nc; it += kSlThreads) {
+    const int g = it / nc, k = it - g * nc;
+    const float* __restrict__ row = tile + g * bins;
+    double acc = 0.0;
+    for (int n = 0; n < bins; ++n) acc = fma((double)row[n], (double)p.dct_t[n * nc + k], acc);
+    dst[it] = (float)acc;
+  }
+}
+
 // dL/d audio from dL/d |STFT(audio)| (`cot` [B, frames, S / 2 + 1]); stft_l1_bwd_block's arithmetic on frames of 3 S / 4 samples
 template <int S>
 __global__ __launch_bounds__(kSlThreads) void stft_tq_cot_bwd_kernel(const float* __restrict__ audio, float* __restrict__ grad_audio,
@@ -1520,6 +1596,32 @@ extern "C" int ddsp_stft_frames_f32(const float* audio, float* spectrum, int B, 
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SFC_CASE
+  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+}
+
+extern "C" int ddsp_mel_features_f32(const float* audio, const int* bands, const float* weights, const float* dct_t, float* out,
+                                     int B, int N, int fft_size, int frame_size, int hop, int pad_left, int n_frames, int bins,
+                                     int mfcc_bins, int n_weights, int mode, float eps, void* stream) {
+  if (!audio || !bands || !weights || !out || (mode == DDSP_MEL_MFCC && !dct_t)) return DDSP_ERR_NULL_POINTER;
+  if (const int rc = sl_frames_geometry_ok(B, N, fft_size, hop, pad_left, n_frames)) return rc;
+  if (bins <= 0 || n_weights < 0 || (mode == DDSP_MEL_MFCC && mfcc_bins <= 0)) return DDSP_ERR_BAD_SHAPE;
+  if (frame_size < 2 || frame_size > fft_size || (frame_size & 1)) return DDSP_ERR_UNSUPPORTED;
+  if (mode < DDSP_MEL_LINEAR || mode > DDSP_MEL_MFCC) return DDSP_ERR_UNSUPPORTED;
+  const int g = 2 * kSlPoints / fft_size;
+  // the [g][bins] tile lies in the transform's 2 kSlPoints floats: bins <= fft_size
+  if ((long long)g * bins > 2 * kSlPoints || (mode == DDSP_MEL_MFCC && mfcc_bins > bins)) return DDSP_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const SlFrameGeom fg = {frame_size, hop, pad_left, 1.0f / (float)frame_size};
+  const SlMelArgs p = {bands, weights, dct_t, bins, mfcc_bins, n_weights, mode, eps};
+  const dim3 grid((unsigned)((n_frames + g - 1) / g), (unsigned)B, 1u);
+#define DDSP_MEL_CASE(SZ) case SZ: hipLaunchKernelGGL((stft_tq_mel_kernel<SZ>), grid, dim3(kSlThreads), 0, st, audio, out, N, \
+                                                      n_frames, fg, p); break
+  switch (fft_size) {
+    DDSP_MEL_CASE(64); DDSP_MEL_CASE(128); DDSP_MEL_CASE(256); DDSP_MEL_CASE(512); DDSP_MEL_CASE(1024);
+    DDSP_MEL_CASE(2048); DDSP_MEL_CASE(4096); DDSP_MEL_CASE(8192);
+    default: return DDSP_ERR_UNSUPPORTED;
+  }
+#undef DDSP_MEL_CASE
   return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
 }
 

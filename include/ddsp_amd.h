@@ -401,6 +401,32 @@ int ddsp_stft_frames_mag_ex_f32(const float* audio, float* mag, int B, int N, in
                                 int n_frames, void* stream);
 int ddsp_stft_frames_mag_backward_f32(const float* audio, const float* grad_mag, float* grad_audio, int B, int N, int fft_size,
                                       int hop, int pad_left, int n_frames, void* stream);
+/* spectral_ops.compute_mel / compute_logmel / compute_mfcc (ddsp/spectral_ops.py:73-133) under the frame geometry of
+ * ddsp_stft_frames_mag_ex_f32, in one kernel: the magnitudes stay on chip, only out [B, n_frames, bins] (DDSP_MEL_LINEAR: the mel
+ * spectrogram; DDSP_MEL_LOG: log(where(mel <= 0, eps, mel))) or [B, n_frames, mfcc_bins] (DDSP_MEL_MFCC: the first mfcc_bins
+ * coefficients of the scaled DCT-II of the log-mel values) is written.  The mel matrix travels by its bands: bands [3][bins]
+ * int32 - first spectrogram bin, number of bins, index of the band's first weight in `weights` (n_weights floats; a band of
+ * no bins is an all-zero column); dct_t [bins][mfcc_bins] is the DCT table, TRANSPOSED (DDSP_MEL_MFCC only, else may be null).
+ * Limits (DDSP_ERR_UNSUPPORTED beyond): bins <= fft_size, mfcc_bins <= bins.  Forward only; bit-reproducible. */
+#define DDSP_MEL_LINEAR 0
+#define DDSP_MEL_LOG 1
+#define DDSP_MEL_MFCC 2
+int ddsp_mel_features_f32(const float* audio, const int* bands, const float* weights, const float* dct_t, float* out, int B, int N,
+                          int fft_size, int frame_size, int hop, int pad_left, int n_frames, int bins, int mfcc_bins,
+                          int n_weights, int mode, float eps, void* stream);
+/* spectral_ops.compute_rms_energy / compute_power (ddsp/spectral_ops.py:223-249): frames of frame_size samples (any size >= 1)
+ * every `hop`, the first pad_left samples before sample 0, zeros outside the row -> out [B, n_frames]: sqrt(mean x^2), or with
+ * DDSP_ENERGY_DB core.amplitude_to_db of it, max(10 log10(max(pmin, rms^2)) - ref_db, -range_db), pmin = 10^(-range_db / 10). */
+#define DDSP_ENERGY_DB 0x1u
+int ddsp_frame_energy_f32(const float* audio, float* out, int B, int N, int frame_size, int hop, int pad_left, int n_frames,
+                          float ref_db, float range_db, unsigned flags, void* stream);
+/* core.power_to_db / amplitude_to_db (p0 = ref_db, p1 = range_db) / db_to_power / db_to_amplitude (ddsp/core.py:247-277) on n
+ * values. */
+#define DDSP_DB_POWER_TO_DB 0
+#define DDSP_DB_AMPLITUDE_TO_DB 1
+#define DDSP_DB_TO_POWER 2
+#define DDSP_DB_TO_AMPLITUDE 3
+int ddsp_db_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream);
 int ddsp_loudness_from_mag_f32(const float* mag, const float* weighting, float* loudness, int B, int n_frames, int bins,
                                float range_db, float ref_db, void* stream);
 int ddsp_loudness_from_mag_backward_f32(const float* mag, const float* weighting, const float* grad_loudness, float* grad_mag,
