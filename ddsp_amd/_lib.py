@@ -139,6 +139,8 @@ SIGNATURES = {
     'ddsp_row_mean_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_voidp]),
     'ddsp_row_mean_backward_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_voidp]),
     'ddsp_unit_convert_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_float, c_voidp]),
+    'ddsp_wasserstein_f32': (c_int, [c_f32p] * 5 + [c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_wasserstein_backward_f32': (c_int, [c_f32p] * 9 + [c_size_t] + [c_int] * 4 + [c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),
@@ -173,7 +175,8 @@ DB_OPS = {'power_to_db': 0, 'amplitude_to_db': 1, 'db_to_power': 2, 'db_to_ampli
 MEL_MODES = {'mel': 0, 'logmel': 1, 'mfcc': 2}
 ENERGY_DB = 0x1
 S2H_NORMALIZE = 0x1
-CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block stages in LDS (csrc/consistency.hip)
+WASSERSTEIN_MIDI = 0x1
+CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block stages in LDS (csrc/consistency.hip, wasserstein.hip)
 CONSISTENCY_MAX_POINTS = 256
 CONSISTENCY_MAX_GAUSSIANS = 4096
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}

@@ -1051,4 +1051,10 @@ DDSP_WEAK int ddsp_frame_energy_f32(const float*, float*, int, int, int, int, in
   return DDSP_ERR_UNSUPPORTED;
 }
 DDSP_WEAK int ddsp_db_convert_f32(const float*, float*, size_t, int, float, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+// and of csrc/wasserstein.hip
+DDSP_WEAK int ddsp_wasserstein_f32(const float*, const float*, const float*, const float*, float*, size_t, int, int, int, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_wasserstein_backward_f32(const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
+                                            float*, size_t, int, int, int, int, void*) { return DDSP_ERR_UNSUPPORTED; }
 #undef DDSP_WEAK

@@ -476,9 +476,10 @@ class _SpectralLossGeneralFunction(torch.autograd.Function):
 
 # --------------------------------------------------------------------------------------
 # Consistency losses (ddsp/losses.py:489-578, 689-1076).  csrc/consistency.hip holds the kernels of KDEConsistencyLoss, TWMLoss
-# and core.sinusoidal_to_harmonic; the thin ones run on mean_difference.  A loss is a sum of up to three 0-dim terms, each the
-# output of a kernel; the terms are added as 0-dim tensors (as SpectralLoss adds its fused and plain parts).
-# Not built: WassersteinConsistencyLoss / wasserstein_distance, EmbeddingLoss, the CREPE classes.
+# and core.sinusoidal_to_harmonic, csrc/wasserstein.hip those of WassersteinConsistencyLoss / wasserstein_distance; the thin
+# ones run on mean_difference.  A loss is a sum of up to three 0-dim terms, each the output of a kernel; the terms are added
+# as 0-dim tensors (as SpectralLoss adds its fused and plain parts).
+# Not built: EmbeddingLoss, the CREPE classes.
 # --------------------------------------------------------------------------------------
 def amp_loss(amp, amp_target, loss_type='L1', weights=None, log=False, amin=1e-5):
   """Loss comparing two amplitudes (scale logarithmically) (ddsp/losses.py:492-504)."""
@@ -751,3 +752,98 @@ class TWMLoss(Loss):
     if core._needs_grad(f0_candidates, freqs, amps):
       return _TwmTensorsFunction.apply(f0_candidates, freqs, amps, args)
     return _TwmTensorsFunction.forward(core._NoCtx(), f0_candidates, freqs, amps, args)
+
+
+class _WassersteinFunction(torch.autograd.Function):
+  """torch.autograd node of wasserstein_distance on [rows, n] tensors (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, u_values, v_values, u_weights, v_weights, p, flags):
+    ctx.save_for_backward(u_values, v_values, u_weights, v_weights)
+    ctx.args = (u_values.shape[1], v_values.shape[1], p, flags)
+    rows = u_values.shape[0]
+    distance = torch.empty((rows,), dtype=torch.float32, device=u_values.device)
+    if rows:
+      rc = _lib.load().ddsp_wasserstein_f32(u_values.data_ptr(), v_values.data_ptr(), _ptr(u_weights), _ptr(v_weights),
+                                            distance.data_ptr(), rows, *ctx.args, core._stream())
+      _lib.check(rc, 'ddsp_wasserstein_f32')
+    return distance
+
+  @staticmethod
+  def backward(ctx, grad_distance):
+    u_values, v_values, u_weights, v_weights = ctx.saved_tensors
+    grad_distance = core.tf_float32(grad_distance)
+    grads = [None if x is None else torch.empty_like(x) for x in (u_values, v_values, u_weights, v_weights)]
+    if u_values.shape[0]:
+      rc = _lib.load().ddsp_wasserstein_backward_f32(u_values.data_ptr(), v_values.data_ptr(), _ptr(u_weights), _ptr(v_weights),
+                                                     grad_distance.data_ptr(), *[_ptr(g) for g in grads], u_values.shape[0],
+                                                     *ctx.args, core._stream())
+      _lib.check(rc, 'ddsp_wasserstein_backward_f32')
+    return grads[0], grads[1], grads[2], grads[3], None, None
+
+
+def _ptr(x):
+  return None if x is None else x.data_ptr()
+
+
+def _wasserstein(u_values, v_values, u_weights, v_weights, p, flags):
+  """wasserstein_distance on contiguous fp32 tensors, [..., n_u] against [..., n_v] -> [...]."""
+  p = float(p)
+  if p not in (1.0, 2.0):
+    raise NotImplementedError('wasserstein_distance is built for p = 1 and p = 2 on the MI355X path, got p = {}'.format(p))
+  names = ('u_values', 'v_values', 'u_weights', 'v_weights')
+  tensors = (u_values, v_values, u_weights, v_weights)
+  shapes = ', '.join('{} {}'.format(n, tuple(t.shape)) for n, t in zip(names, tensors) if t is not None)
+  if u_values.dim() < 1 or v_values.dim() < 1 or u_values.shape[:-1] != v_values.shape[:-1]:
+    raise ValueError('expected [..., n] tensors with equal batch shapes, got ' + shapes)
+  for values, weights in ((u_values, u_weights), (v_values, v_weights)):
+    if weights is not None and weights.shape != values.shape:
+      raise ValueError('weights must have the shape of their values, got ' + shapes)
+  n_u, n_v = u_values.shape[-1], v_values.shape[-1]
+  if n_u < 1 or n_v < 1:
+    raise ValueError('the last axes must not be empty, got ' + shapes)
+  if max(n_u, n_v) > _lib.CONSISTENCY_MAX_K:
+    raise NotImplementedError('wasserstein_distance takes up to {} samples a side on the MI355X path, got {} and {}'.format(
+        _lib.CONSISTENCY_MAX_K, n_u, n_v))
+  batch = u_values.shape[:-1]
+  args = [None if t is None else t.reshape(-1, t.shape[-1]) for t in tensors] + [int(p), flags]
+  if core._needs_grad(*tensors):
+    return _WassersteinFunction.apply(*args).reshape(batch)
+  return _WassersteinFunction.forward(core._NoCtx(), *args).reshape(batch)
+
+
+def wasserstein_distance(u_values, v_values, u_weights, v_weights, p=1.0):
+  """Differentiable 1-D Wasserstein distance (ddsp/losses.py:632-686), adapted there from scipy.stats.
+
+  u_values [..., n_u], v_values [..., n_v] with equal batch shapes; u_weights / v_weights of their values' shapes, or None;
+  p: 1 (Wasserstein) or 2 (energy) -> [...].  As in the reference THE WEIGHTS ARE NOT NORMALISED (it computes the normalised
+  CDF and drops the result): only a side with weights=None has a CDF that ends at 1.  One fused kernel per direction
+  (csrc/wasserstein.hip: a block per row sorts, scans and reduces in LDS); up to 1024 samples a side."""
+  u_values, v_values = core.tf_float32(u_values), core.tf_float32(v_values)
+  u_weights = None if u_weights is None else core.tf_float32(u_weights)
+  v_weights = None if v_weights is None else core.tf_float32(v_weights)
+  return _wasserstein(u_values, v_values, u_weights, v_weights, p, 0)
+
+
+class WassersteinConsistencyLoss(Loss):
+  """Compare similarity of two traces of sinusoids using wasserstein distance (ddsp/losses.py:584-629; EXPERIMENTAL there).
+
+  The mean over [batch, time] of weight * wasserstein_distance(hz_to_midi(freqs_a), hz_to_midi(freqs_b), amps_a, amps_b, p=1).
+  Two quirks of the reference are kept: the amplitudes weigh the frequencies WITHOUT being normalised (see
+  wasserstein_distance), and the distance is computed only inside `if self.midi:` - with midi=False, as with weight <= 0,
+  the loss is the float 0.0.  hz_to_midi is taken inside the kernel: no MIDI tensor is built.  Up to 1024 sinusoids a side."""
+
+  def __init__(self, weight=1.0, midi=True, name='wasserstein_consistency_loss'):
+    super().__init__(name=name)
+    self.weight = weight
+    self.midi = midi
+
+  def call(self, amps_a, freqs_a, amps_b, freqs_b):
+    """Scalar, weighted wasserstein distance."""
+    loss = 0.0
+    if self.weight > 0.0 and self.midi:
+      amps_a, freqs_a = _sinusoid_frames(('amps_a', 'freqs_a'), (amps_a, freqs_a))
+      amps_b, freqs_b = _sinusoid_frames(('amps_b', 'freqs_b'), (amps_b, freqs_b))
+      _sinusoid_frames(('amps_a', 'amps_b'), (amps_a, amps_b), same_last=False)
+      loss = core._mean(_wasserstein(freqs_a, freqs_b, amps_a, amps_b, 1.0, _lib.WASSERSTEIN_MIDI), self.weight)
+    return loss

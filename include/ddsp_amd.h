@@ -785,6 +785,31 @@ int ddsp_unit_convert_backward_f32(const float* in, const float* grad_out, float
                                    float p1, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * losses.wasserstein_distance (ddsp/losses.py:632-686) and, with DDSP_WASSERSTEIN_MIDI, the per-frame distance of
+ * WassersteinConsistencyLoss (:584-629): csrc/wasserstein.hip.  A block owns a row: the row's n_u + n_v values are ranked,
+ * scanned and reduced in LDS; no call needs a workspace, nothing of size [rows, n_u + n_v] is built, forward or backward.
+ * No atomics: the same bits on every run and for any subset of the rows.
+ *
+ * ddsp_wasserstein_f32: u_values [rows, n_u], v_values [rows, n_v], u_weights [rows, n_u] or NULL, v_weights [rows, n_v] or
+ *   NULL -> distance [rows] = (sum_i delta_i |U_i - V_i|^p)^(1/p) over the stably sorted concatenation of the values.  The
+ *   weights are used as they are, NOT normalised (the reference computes the normalised CDF and drops it); a NULL side has
+ *   the CDF index / n_side.  A row with a NaN among its values or weights gives NaN; the other rows are unaffected.
+ *   flags: DDSP_WASSERSTEIN_MIDI - the values are frequencies in Hz and are compared as hz_to_midi(value) (f <= 0 -> 0).
+ * ddsp_wasserstein_backward_f32: the same inputs and grad_distance [rows] -> grad_u_values, grad_v_values, and grad_u_weights /
+ *   grad_v_weights (NULL exactly where the weights are NULL, else DDSP_ERR_NULL_POINTER).  It recomputes the forward pass;
+ *   every gradient element is written once.  Among exactly tied values the gradient of a value is one of the valid
+ *   one-sided choices (the sum over a group of tied values is the group's derivative).
+ * Bounds (DDSP_ERR_UNSUPPORTED beyond): n_u, n_v <= 1024 each; p = 1 or 2.  The ranking compares every pair of a row's
+ * values: its cost is quadratic in n_u + n_v.
+ */
+#define DDSP_WASSERSTEIN_MIDI 0x1
+int ddsp_wasserstein_f32(const float* u_values, const float* v_values, const float* u_weights, const float* v_weights,
+                         float* distance, size_t rows, int n_u, int n_v, int p, int flags, void* stream);
+int ddsp_wasserstein_backward_f32(const float* u_values, const float* v_values, const float* u_weights, const float* v_weights,
+                                  const float* grad_distance, float* grad_u_values, float* grad_v_values, float* grad_u_weights,
+                                  float* grad_v_weights, size_t rows, int n_u, int n_v, int p, int flags, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
