@@ -141,6 +141,14 @@ SIGNATURES = {
     'ddsp_unit_convert_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_wasserstein_f32': (c_int, [c_f32p] * 5 + [c_size_t] + [c_int] * 4 + [c_voidp]),
     'ddsp_wasserstein_backward_f32': (c_int, [c_f32p] * 9 + [c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_fft_convolve_grad_audio_f32': (c_int, [c_f32p] * 3 + [c_int] * 7 + [c_voidp]),
+    'ddsp_fft_convolve_grad_ir_f32': (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_voidp]),
+    'ddsp_sinc_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_float, c_voidp]),
+    'ddsp_sinc_impulse_response_size': (c_int, [c_int]),
+    'ddsp_sinc_impulse_response_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_float, c_int, c_voidp]),
+    'ddsp_sinc_impulse_response_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_int, c_voidp]),
+    'ddsp_frequency_impulse_response_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_int, c_voidp]),
+    'ddsp_exp_sigmoid_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t] + [c_float] * 3 + [c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),

@@ -164,13 +164,36 @@ def nested_lookup(nested_key, nested_dict, delimiter='/'):
 def exp_sigmoid(x, exponent=10.0, max_value=2.0, threshold=1e-7):
   """Exponentiated sigmoid: max_value * sigmoid(x)**log(exponent) + threshold."""
   x = tf_float32(x)
-  require_no_grad('core.exp_sigmoid', x)
+  if _needs_grad(x):
+    return _ExpSigmoidFunction.apply(x, float(exponent), float(max_value), float(threshold))
+  return _exp_sigmoid_run(x, float(exponent), float(max_value), float(threshold))
+
+
+def _exp_sigmoid_run(x, exponent, max_value, threshold):
   out = torch.empty_like(x)
-  rc = _lib.load().ddsp_exp_sigmoid_f32(x.data_ptr(), out.data_ptr(), x.numel(),
-                                        float(exponent), float(max_value), float(threshold),
-                                        _stream())
+  rc = _lib.load().ddsp_exp_sigmoid_f32(x.data_ptr(), out.data_ptr(), x.numel(), exponent, max_value, threshold, _stream())
   _lib.check(rc, 'ddsp_exp_sigmoid_f32')
   return out
+
+
+class _ExpSigmoidFunction(torch.autograd.Function):
+  """torch.autograd node of core.exp_sigmoid (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, x, exponent, max_value, threshold):
+    ctx.save_for_backward(x)
+    ctx.constants = (exponent, max_value, threshold)
+    return _exp_sigmoid_run(x.detach(), exponent, max_value, threshold)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    x, = ctx.saved_tensors
+    grad_out = tf_float32(grad_out)
+    grad_in = torch.empty_like(x)
+    rc = _lib.load().ddsp_exp_sigmoid_backward_f32(x.data_ptr(), grad_out.data_ptr(), grad_in.data_ptr(), x.numel(),
+                                                   *ctx.constants, _stream())
+    _lib.check(rc, 'ddsp_exp_sigmoid_backward_f32')
+    return grad_in, None, None, None
 
 
 def safe_divide(numerator, denominator, eps=1e-7):
@@ -682,18 +705,65 @@ def frequency_impulse_response(magnitudes, window_size=0):
   """core.frequency_impulse_response: [B,F,M] (or [B,M]) magnitudes -> causal windowed IR."""
   magnitudes = tf_float32(magnitudes)
   squeeze = magnitudes.dim() == 2
-  require_no_grad('core.frequency_impulse_response (FilteredNoise is the differentiable entry)', magnitudes)
   if squeeze:
     magnitudes = magnitudes[:, None, :].contiguous()
+  if _needs_grad(magnitudes):
+    ir = _FrequencyImpulseResponseFunction.apply(magnitudes, int(window_size))
+  else:
+    ir = _frequency_impulse_response_run(magnitudes, int(window_size))
+  return ir[:, 0, :] if squeeze else ir
+
+
+def _frequency_impulse_response_run(magnitudes, window_size):
   b, f, m = magnitudes.shape
   lib = _lib.load()
-  size = lib.ddsp_fir_size(m, int(window_size))
+  size = lib.ddsp_fir_size(m, window_size)
   _lib.check(min(size, 0), 'ddsp_fir_size')
   ir = torch.empty((b, f, size), dtype=torch.float32, device=magnitudes.device)
-  rc = lib.ddsp_frequency_impulse_response_f32(magnitudes.data_ptr(), ir.data_ptr(), b, f, m,
-                                               int(window_size), _stream())
+  rc = lib.ddsp_frequency_impulse_response_f32(magnitudes.data_ptr(), ir.data_ptr(), b, f, m, window_size, _stream())
   _lib.check(rc, 'ddsp_frequency_impulse_response_f32')
-  return ir[:, 0, :] if squeeze else ir
+  return ir
+
+
+_design_cache = {}
+
+
+def _fir_design(n_bands, window_size, device):
+  """The design of frequency_impulse_response as a matrix [ir_size, n_bands]: it is linear in the magnitudes, so its columns
+  are the impulse responses of the unit magnitude vectors - made by the forward kernel itself, once per (bands, window,
+  device).  The backward pass multiplies by its transpose (ddsp_frequency_impulse_response_backward_f32)."""
+  key = (n_bands, window_size, str(device))
+  design = _design_cache.get(key)
+  if design is None:
+    with torch.no_grad():
+      unit = torch.eye(n_bands, dtype=torch.float32, device=device)[None].contiguous()
+      design = _frequency_impulse_response_run(unit, window_size)[0].t().contiguous()
+    _design_cache[key] = design
+  return design
+
+
+class _FrequencyImpulseResponseFunction(torch.autograd.Function):
+  """torch.autograd node of core.frequency_impulse_response (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, magnitudes, window_size):
+    ctx.shape, ctx.window_size = tuple(magnitudes.shape), window_size
+    return _frequency_impulse_response_run(magnitudes.detach(), window_size)
+
+  @staticmethod
+  def backward(ctx, grad_ir):
+    b, f, m = ctx.shape
+    grad_ir = tf_float32(grad_ir)
+    size = int(grad_ir.shape[-1])
+    design = _fir_design(m, ctx.window_size, grad_ir.device)
+    grad_mag = torch.empty(ctx.shape, dtype=torch.float32, device=grad_ir.device)
+    rc = _lib.load().ddsp_frequency_impulse_response_backward_f32(grad_ir.data_ptr(), design.data_ptr(), grad_mag.data_ptr(),
+                                                                  b * f, m, size, _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+      raise NotImplementedError('the backward pass of frequency_impulse_response holds impulse responses of at most 12288 taps, '
+                                'got {}'.format(size))
+    _lib.check(rc, 'ddsp_frequency_impulse_response_backward_f32')
+    return grad_mag, None
 
 
 def apply_window_to_impulse_response(impulse_response, window_size=0, causal=False):
@@ -742,8 +812,6 @@ def fft_convolve(audio, impulse_response, padding='same', delay_compensation=-1)
   audio, impulse_response = tf_float32(audio), tf_float32(impulse_response)
   if audio.dim() != 2:
     raise ValueError('audio must be [batch, audio_timesteps], got {}'.format(tuple(audio.shape)))
-  require_no_grad('core.fft_convolve (effects.Reverb / FilteredNoise are the differentiable entries)', audio,
-                  impulse_response)
   batch_size, audio_size = audio.shape
   if impulse_response.dim() == 2:
     impulse_response = impulse_response[:, None, :].contiguous()
@@ -759,6 +827,18 @@ def fft_convolve(audio, impulse_response, padding='same', delay_compensation=-1)
   start_requested, start, n_out = _crop_range(audio_size, n_ir_frames, ir_size, padding, delay_compensation)
   if n_out == 0:
     return torch.empty((batch_size, 0), dtype=torch.float32, device=audio.device)
+  crop = (start_requested, start, n_out, int(delay_compensation))
+  if _needs_grad(audio, impulse_response):
+    return _FftConvolveFunction.apply(audio, impulse_response, crop)
+  return _fft_convolve_run(audio, impulse_response, crop)
+
+
+def _fft_convolve_run(audio, impulse_response, crop):
+  """fft_convolve on checked arguments: audio [B, N], impulse_response [B or 1, F, L], crop = (start as requested, first kept
+  index, number of kept samples, delay_compensation)."""
+  start_requested, start, n_out, delay_compensation = crop
+  batch_size, audio_size = audio.shape
+  batch_size_ir, n_ir_frames, ir_size = impulse_response.shape
   if n_ir_frames == 1 and ir_size > LONG_IR_TAPS:
     # one long IR (a reverb): partitioned FFT convolution instead of the direct FIR
     return fft_convolve_long(audio, impulse_response[:, 0, :], delay=start, n_out=n_out)
@@ -777,6 +857,74 @@ def fft_convolve(audio, impulse_response, padding='same', delay_compensation=-1)
         n_ir_frames, ir_size, audio_size, n_out, start, _stream())
     _lib.check(rc, 'ddsp_fft_convolve_f32')
   return out
+
+
+def _sum_rows(x, n_rows):
+  """[n_rows, ...] -> [1, ...]: the rows added in row order (ddsp_sum_rows_f32)."""
+  out = torch.empty((1,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+  _lib.check(_lib.load().ddsp_sum_rows_f32(x.data_ptr(), out.data_ptr(), n_rows, x.numel() // n_rows, 0, _stream()),
+             'ddsp_sum_rows_f32')
+  return out
+
+
+def _fft_convolve_backward(audio, impulse_response, grad_out, crop, need_audio, need_ir):
+  """dL/d audio [B, N] and dL/d impulse_response [B or 1, F, L] of _fft_convolve_run: the two correlations of
+  csrc/fir_grad.hip; for the one long impulse response of the FFT route the same two as FFT convolutions with reversed
+  indices, as effects.Reverb runs them."""
+  _, start, n_out, _ = crop
+  b, n = audio.shape
+  b_ir, f, l = impulse_response.shape
+  g = tf_float32(grad_out)
+  lib = _lib.load()
+  grad_audio = grad_ir = None
+  if f == 1 and l > LONG_IR_TAPS:
+    if need_audio:       # dL/d audio = reverse(conv(reverse(g), ir)[n_out - N + start : n_out + start])
+      grad_audio = fft_convolve_long(g, impulse_response[:, 0, :], delay=n_out - n + start, n_out=n, reverse_audio=True,
+                                     reverse_out=True)
+    if need_ir:          # dL/d ir[k] = conv(g, reverse(audio))[N - 1 - start + k]; taps below start - N + 1 meet no output
+      k0 = max(0, start - n + 1)
+      grad_ir = torch.zeros((b, 1, l), dtype=torch.float32, device=g.device) if k0 else None
+      if l > k0:
+        part = fft_convolve_long(g, audio, delay=n - 1 - start + k0, n_out=l - k0, reverse_ir=True)
+        if k0:
+          grad_ir[:, 0, k0:] = part
+        else:
+          grad_ir = part[:, None, :]
+  else:
+    if need_audio:
+      grad_audio = torch.empty((b, n), dtype=torch.float32, device=g.device)
+      rc = lib.ddsp_fft_convolve_grad_audio_f32(g.data_ptr(), impulse_response.data_ptr(), grad_audio.data_ptr(), b, b_ir, f, l, n,
+                                                n_out, start, _stream())
+      if rc == _lib.ERR_UNSUPPORTED:
+        raise NotImplementedError('the backward pass of fft_convolve holds at most 65535 rows, got {}'.format(b))
+      _lib.check(rc, 'ddsp_fft_convolve_grad_audio_f32')
+    if need_ir:
+      grad_ir = torch.empty((b, f, l), dtype=torch.float32, device=g.device)
+      rc = lib.ddsp_fft_convolve_grad_ir_f32(g.data_ptr(), audio.data_ptr(), grad_ir.data_ptr(), b, f, l, n, n_out, start, _stream())
+      if rc == _lib.ERR_UNSUPPORTED:
+        raise NotImplementedError('the backward pass of fft_convolve holds at most 65535 rows and 65535 frames, got {} and {}'
+                                  .format(b, f))
+      _lib.check(rc, 'ddsp_fft_convolve_grad_ir_f32')
+  if grad_ir is not None and b_ir == 1 and b > 1:
+    grad_ir = _sum_rows(grad_ir.contiguous(), b)       # one impulse response for the batch collects the rows' gradients
+  return grad_audio, grad_ir
+
+
+class _FftConvolveFunction(torch.autograd.Function):
+  """torch.autograd node of core.fft_convolve (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, audio, impulse_response, crop):
+    ctx.save_for_backward(audio, impulse_response)
+    ctx.crop = crop
+    return _fft_convolve_run(audio.detach(), impulse_response.detach(), crop)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    audio, impulse_response = ctx.saved_tensors
+    grad_audio, grad_ir = _fft_convolve_backward(audio.detach(), impulse_response.detach(), grad_out, ctx.crop,
+                                                 ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+    return grad_audio, grad_ir, None
 
 
 LONG_IR_TAPS = 1024       # single-frame IRs longer than this take the FFT path
@@ -838,6 +986,77 @@ def _check_frames(audio_size, n_ir_frames):
 def frequency_filter(audio, magnitudes, window_size=0, padding='same'):
   """core.frequency_filter = fft_convolve(audio, frequency_impulse_response(magnitudes))."""
   impulse_response = frequency_impulse_response(magnitudes, window_size=window_size)
+  return fft_convolve(audio, impulse_response, padding=padding)
+
+
+def sinc(x, threshold=1e-20):
+  """core.sinc (ddsp/core.py:1568-1573): sin(pi x) / (pi x), |x| < threshold replaced by threshold.  Forward only on its own
+  (sinc_impulse_response / sinc_filter are the differentiable entries)."""
+  x = tf_float32(x)
+  require_no_grad('core.sinc (sinc_impulse_response / sinc_filter are the differentiable entries)', x)
+  out = torch.empty_like(x)
+  _lib.check(_lib.load().ddsp_sinc_f32(x.data_ptr(), out.data_ptr(), x.numel(), float(threshold), _stream()), 'ddsp_sinc_f32')
+  return out
+
+
+def _sinc_ir_run(cutoff, window_size, sample_rate, high_pass, size):
+  ir = torch.empty(tuple(cutoff.shape[:-1]) + (size,), dtype=torch.float32, device=cutoff.device)
+  rc = _lib.load().ddsp_sinc_impulse_response_f32(cutoff.data_ptr(), ir.data_ptr(), cutoff.numel(), window_size, sample_rate,
+                                                  1 if high_pass else 0, _stream())
+  _lib.check(rc, 'ddsp_sinc_impulse_response_f32')
+  return ir
+
+
+class _SincImpulseResponseFunction(torch.autograd.Function):
+  """torch.autograd node of core.sinc_impulse_response (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, cutoff, window_size, sample_rate, high_pass, size):
+    ctx.save_for_backward(cutoff)
+    ctx.args = (window_size, sample_rate, 1 if high_pass else 0)
+    return _sinc_ir_run(cutoff.detach(), window_size, sample_rate, high_pass, size)
+
+  @staticmethod
+  def backward(ctx, grad_ir):
+    cutoff, = ctx.saved_tensors
+    grad_ir = tf_float32(grad_ir)
+    grad_cutoff = torch.empty_like(cutoff)
+    rc = _lib.load().ddsp_sinc_impulse_response_backward_f32(cutoff.data_ptr(), grad_ir.data_ptr(), grad_cutoff.data_ptr(),
+                                                             cutoff.numel(), *ctx.args, _stream())
+    _lib.check(rc, 'ddsp_sinc_impulse_response_backward_f32')
+    return grad_cutoff, None, None, None, None
+
+
+def sinc_impulse_response(cutoff_frequency, window_size=512, sample_rate=None, high_pass=False):
+  """core.sinc_impulse_response (ddsp/core.py:1576-1625): cutoff_frequency [batch, n_time, 1] (Hertz when sample_rate is
+  given, else a fraction of Nyquist; a scalar gives one filter, [1, 1, size]) -> Hamming-windowed sinc low-pass (high_pass:
+  spectrally inverted) impulse responses [batch, n_time, (window_size // 2) * 2 + 1], normalised to unit gain.  The caller's
+  tensor is left as it is (the reference scales a numpy argument in place).  Differentiable in cutoff_frequency."""
+  cutoff = tf_float32(cutoff_frequency)
+  if cutoff.dim() == 0:
+    cutoff = cutoff.reshape(1, 1, 1)
+  if cutoff.dim() != 3 or cutoff.shape[-1] != 1:
+    raise ValueError('cutoff_frequency must be [batch_size, n_time, 1] or a scalar, got {}'.format(tuple(cutoff.shape)))
+  window_size = int(window_size)
+  if window_size < 0:
+    raise ValueError('window_size must not be negative, got {}'.format(window_size))
+  if sample_rate is not None and not float(sample_rate) > 0.0:
+    raise ValueError('sample_rate must be positive, got {}'.format(sample_rate))
+  rate = 0.0 if sample_rate is None else float(sample_rate)
+  size = (window_size // 2) * 2 + 1
+  if cutoff.numel() == 0:
+    return torch.empty(tuple(cutoff.shape[:-1]) + (size,), dtype=torch.float32, device=cutoff.device)
+  if _needs_grad(cutoff):
+    return _SincImpulseResponseFunction.apply(cutoff, window_size, rate, bool(high_pass), size)
+  return _sinc_ir_run(cutoff, window_size, rate, bool(high_pass), size)
+
+
+def sinc_filter(audio, cutoff_frequency, window_size=512, sample_rate=None, padding='same', high_pass=False):
+  """core.sinc_filter (ddsp/core.py:1658-1690) = fft_convolve(audio, sinc_impulse_response(cutoff_frequency, ...)) with the
+  default delay compensation, which takes window_size // 2 - 1 samples off the start: the output lags the input by one
+  sample, as the reference's does.  Differentiable in audio and cutoff_frequency."""
+  impulse_response = sinc_impulse_response(cutoff_frequency, window_size=window_size, sample_rate=sample_rate,
+                                           high_pass=high_pass)
   return fft_convolve(audio, impulse_response, padding=padding)
 
 

@@ -1057,4 +1057,23 @@ DDSP_WEAK int ddsp_wasserstein_f32(const float*, const float*, const float*, con
 }
 DDSP_WEAK int ddsp_wasserstein_backward_f32(const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
                                             float*, size_t, int, int, int, int, void*) { return DDSP_ERR_UNSUPPORTED; }
+// and of csrc/fir_grad.hip
+DDSP_WEAK int ddsp_fft_convolve_grad_audio_f32(const float*, const float*, float*, int, int, int, int, int, int, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_fft_convolve_grad_ir_f32(const float*, const float*, float*, int, int, int, int, int, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_sinc_f32(const float*, float*, size_t, float, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinc_impulse_response_size(int) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinc_impulse_response_f32(const float*, float*, size_t, int, float, int, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_sinc_impulse_response_backward_f32(const float*, const float*, float*, size_t, int, float, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_frequency_impulse_response_backward_f32(const float*, const float*, float*, size_t, int, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_exp_sigmoid_backward_f32(const float*, const float*, float*, size_t, float, float, float, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
 #undef DDSP_WEAK

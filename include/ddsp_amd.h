@@ -505,6 +505,50 @@ int ddsp_resample_ex_backward_f32(const float* grad_out, float* grad_in, int B, 
 int ddsp_fft_convolve_f32(const float* audio, const float* impulse_response, float* out, int B, int Bir,
                           int F, int L, int N, int n_out, int start, void* stream);
 
+/* The adjoint of ddsp_fft_convolve_f32 (what tf.GradientTape forms through core.fft_convolve, ddsp/core.py:1382-1473, and
+ * crop_and_compensate_delay, :1338-1379; effects.FIRFilter, ddsp/effects.py:283-324, trains through it).  With
+ * frame(i) = i / frame_size, frame_size = ceil(N/F), and grad_out [B,n_out] = dL/d out (terms whose grad_out index leaves
+ * [0, n_out) drop):
+ *     grad_audio[b][i]               = sum_k ir[b or 0][frame(i)][k] * grad_out[b][i + k - start]
+ *     grad_impulse_response[b][f][k] = sum_{i in frame f} audio[b][i] * grad_out[b][i + k - start]
+ * impulse_response [Bir,F,L], Bir == B or 1; grad_audio [B,N]; grad_impulse_response [B,F,L] - one per row: for a
+ * broadcast response (Bir == 1) add the rows with ddsp_sum_rows_f32(x, out, B, F*L, 0).  Any (F, L, N, n_out, start >= 0):
+ * grad_audio runs a kernel with the taps of a tile's frames in LDS, or one thread per sample where those do not fit.
+ * No atomics, fixed summation order: the same bits on every call.  B > 65535 (grad_ir also F > 65535): DDSP_ERR_UNSUPPORTED.
+ * (csrc/fir_grad.hip) */
+int ddsp_fft_convolve_grad_audio_f32(const float* grad_out, const float* impulse_response, float* grad_audio, int B, int Bir,
+                                     int F, int L, int N, int n_out, int start, void* stream);
+int ddsp_fft_convolve_grad_ir_f32(const float* grad_out, const float* audio, float* grad_impulse_response, int B, int F, int L,
+                                  int N, int n_out, int start, void* stream);
+
+/* core.sinc_impulse_response (ddsp/core.py:1576-1625; core.sinc :1568-1573): cutoff_frequency [rows] (the reference's
+ * [B,T,1]) -> impulse_response [rows, L], L = ddsp_sinc_impulse_response_size(window_size) = 2 (window_size / 2) + 1:
+ *     c = cutoff * 2 / sample_rate (sample_rate > 0; sample_rate == 0 is the reference's None: c = cutoff),
+ *     x_j = c (j - half), |x_j| < 1e-20 replaced by 1e-20;  s_j = sin(pi x_j) / (pi x_j);
+ *     w_j = 0.54 - 0.46 cos(2 pi j / (L - 1))   (tf.signal.hamming_window(L): L is odd, and TensorFlow's windows of odd
+ *           length divide by L - 1 whether periodic or not; L == 1: [1.0]);
+ *     h_j = w_j s_j / |sum_j w_j s_j|;   high_pass != 0: h_j <- delta(j, half) - h_j.
+ * _backward: grad_impulse_response [rows, L] -> grad_cutoff_frequency [rows], through the quotient, the abs (the sign of
+ * the sum) and the high-pass negation; its sums run in fp64 in a fixed order.  (csrc/fir_grad.hip) */
+int ddsp_sinc_f32(const float* in, float* out, size_t n, float threshold, void* stream);   /* core.sinc on n values */
+int ddsp_sinc_impulse_response_size(int window_size);
+int ddsp_sinc_impulse_response_f32(const float* cutoff_frequency, float* impulse_response, size_t rows, int window_size,
+                                   float sample_rate, int high_pass, void* stream);
+int ddsp_sinc_impulse_response_backward_f32(const float* cutoff_frequency, const float* grad_impulse_response,
+                                            float* grad_cutoff_frequency, size_t rows, int window_size, float sample_rate,
+                                            int high_pass, void* stream);
+
+/* The adjoint of ddsp_frequency_impulse_response_f32 (core.frequency_impulse_response, ddsp/core.py:1534-1565), which is
+ * linear in the magnitudes: grad_magnitudes[r][m] = sum_k design[k][m] * grad_impulse_response[r][k], with design [L,M] =
+ * the impulse responses of the M unit magnitude vectors, transposed.  L <= 12288, else DDSP_ERR_UNSUPPORTED.
+ * (csrc/fir_grad.hip) */
+int ddsp_frequency_impulse_response_backward_f32(const float* grad_impulse_response, const float* design, float* grad_magnitudes,
+                                                 size_t rows, int M, int L, void* stream);
+
+/* The adjoint of ddsp_exp_sigmoid_f32: grad_in = grad_out * log(exponent) * (y - threshold) * (1 - sigmoid(in)), elementwise. */
+int ddsp_exp_sigmoid_backward_f32(const float* in, const float* grad_out, float* grad_in, size_t n, float exponent,
+                                  float max_value, float threshold, void* stream);
+
 /* out[i] = x[i] * scale[0] (scale: one float in device memory): the upstream scalar of a loss's backward pass applied
  * to a stored gradient - the chain rule tf.GradientTape applies through SpectralLoss (ddsp/training/trainers.py:162-171). */
 int ddsp_scale_f32(const float* x, const float* scale, float* out, size_t n, void* stream);
