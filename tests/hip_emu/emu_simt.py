@@ -7,22 +7,28 @@ substitutions the host language needs:
   * the four `asm volatile(...)` statements of harmonic.hip (pairs of scalar row loads with their wait, one
     `s_waitcnt vmcnt(0)`) -> the same loads / a wavefront join in C++.
 Nothing in ddsp_amd/ ever loads this; it exists so that kernel logic can be checked on the CPU when no GPU
-(or no GPU budget) is at hand."""
+(or no GPU budget) is at hand.
+
+There is ONE emulated library, made of the very list of sources the product build compiles, and one harness that points the
+Python layer of ddsp_amd at it: emulated() is the context manager, ddsp_fixture() wraps it as the `ddsp` fixture of the
+tests/test_*_emulated.py modules, and reexport() hands such a module the test functions of the GPU modules it re-runs."""
+import contextlib
 import ctypes
 import hashlib
 import os
 import re
 import subprocess
 
-from ddsp_amd import _lib
+import torch
+
+from ddsp_amd import _lib, core
+from ddsp_amd.build import SOURCES            # the product's own list: the two builds cannot disagree about what the library is
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, 'ddsp_amd', 'csrc')
 BUILD = os.path.join(HERE, '_build', 'simt')
 OUT = os.path.join(BUILD, 'libddsp_simt_emu.so')
-SOURCES = ['harmonic.hip', 'harmonic_table.hip', 'harmonic_bwd_table.hip', 'filtered_noise.hip', 'filtered_noise_mfma.hip', 'filtered_noise_general.hip', 'reverb.hip', 'spectral_loss.hip', 'spectral_terms.hip', 'general.hip',
-           'profile.hip']
 CLANG = '/opt/rocm/lib/llvm/bin/clang++'
 
 _DYN_LDS = re.compile(r'extern\s+__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?([A-Za-z_][\w:]*)\s+(\w+)\[\];')
@@ -100,8 +106,57 @@ def load():
   if _emu is None:
     lib = ctypes.CDLL(build())
     for name, (restype, argtypes) in _lib.SIGNATURES.items():
-      if hasattr(lib, name):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+      fn = getattr(lib, name)                             # every entry point of the header, as in _lib.load()
+      fn.restype, fn.argtypes = restype, argtypes
     _emu = lib
   return _emu
+
+
+@contextlib.contextmanager
+def emulated(*gpu_modules):
+  """Points ddsp_amd at the emulated library and at host memory, and the given GPU test modules at DEV = 'cpu'; puts
+  everything back on the way out, also when the body raises.  The two caches of core hold what the DEVICE library answered
+  (workspace sizes) or made (FIR designs, tensors on the device), so they are set aside and start empty here."""
+  lib = load()
+  saved = (_lib.load, core._device, core._stream, dict(core._ws_bytes_cache), dict(core._design_cache),
+           [module.DEV for module in gpu_modules])
+  try:
+    _lib.load = lambda: lib
+    core._device = lambda: torch.device('cpu')
+    core._stream = lambda: None
+    core._ws_bytes_cache.clear()
+    core._design_cache.clear()
+    for module in gpu_modules:
+      module.DEV = 'cpu'
+    yield lib
+  finally:
+    _lib.load, core._device, core._stream = saved[:3]
+    for cache, was in ((core._ws_bytes_cache, saved[3]), (core._design_cache, saved[4])):
+      cache.clear()
+      cache.update(was)
+    for module, dev in zip(gpu_modules, saved[5]):
+      module.DEV = dev
+
+
+def ddsp_fixture(*gpu_modules):
+  """The module-scoped `ddsp` fixture of an emulated test module: ddsp_amd under emulated(*gpu_modules)."""
+  import pytest
+
+  @pytest.fixture(scope='module')
+  def ddsp():
+    import ddsp_amd
+    os.environ.setdefault('DDSP_EMU_CUS', '4')        # the emulated chip's CU count (persistent kernels size their grid by it)
+    if not os.path.exists(CLANG):
+      pytest.skip('the SIMT emulation builds with the ROCm clang++ (%s), which this machine does not have' % CLANG)
+    with emulated(*gpu_modules):
+      yield ddsp_amd
+  return ddsp
+
+
+def reexport(namespace, *gpu_modules):
+  """Every test function of the GPU modules into `namespace` (the emulated module's globals()) under its own name, so that its
+  parametrisation comes along."""
+  for module in gpu_modules:
+    for name in dir(module):
+      if name.startswith('test_') and callable(getattr(module, name)):
+        namespace[name] = getattr(module, name)

@@ -3,82 +3,13 @@ INFRASTRUCTURE, see tests/test_simt_emulated.py): kernel logic - the frame loads
 the banded mel sums, the log and DCT on the tile, the wavefront sums of the energy kernel - checked without GPU time.  It
 does not replace the `-m gpu` run.
 
-tests/hip_emu/emu_simt.py compiles its own list of sources (spectral_loss.hip, where the mel kernel lives, is on it); this
-module builds a second emulated library from that list plus features.hip, with emu_simt's own preprocessing and flags, under
-its own output path."""
-import ctypes
-import fcntl
-import hashlib
-import os
-import subprocess
-
-import pytest
-import torch
-
+The kernels come from the one emulated library of tests/hip_emu/emu_simt.py, which is built from the product's own list of
+sources; the `ddsp` fixture is emu_simt's harness with this module's GPU tests pointed at host memory."""
 import test_gpu_features as G
-from ddsp_amd import _lib, core
 from tests.hip_emu import emu_simt
 
-SOURCES = emu_simt.SOURCES + ['features.hip']
-BUILD = os.path.join(emu_simt.HERE, '_build', 'simt_features')
-OUT = os.path.join(BUILD, 'libddsp_simt_features_emu.so')
-
-
-def _build():
-  os.makedirs(BUILD, exist_ok=True)
-  with open(os.path.join(BUILD, '.lock'), 'w') as lock:
-    fcntl.flock(lock, fcntl.LOCK_EX)
-    digest = hashlib.sha256((emu_simt._digest() + ' '.join(SOURCES)).encode()).hexdigest()
-    stamp = OUT + '.stamp'
-    if os.path.exists(OUT) and os.path.exists(stamp) and open(stamp).read().strip() == digest:
-      return OUT
-    staged = []
-    for name in os.listdir(emu_simt.CSRC):
-      with open(os.path.join(emu_simt.CSRC, name)) as f:
-        text = f.read()
-      dst = os.path.join(BUILD, name.replace('.hip', '.cpp'))
-      with open(dst, 'w') as f:
-        f.write(emu_simt._preprocess(text))
-      if name in SOURCES:
-        staged.append(dst)
-    include = os.path.join(emu_simt.HERE, 'include_simt')
-    cmd = [emu_simt.CLANG, '-std=c++17', '-O1', '-g0', '-ffp-contract=fast-honor-pragmas', '-mfma', '-shared', '-fPIC', '-w',
-           '-I' + include, '-I' + os.path.join(emu_simt.ROOT, 'include'),
-           '-include', os.path.join(include, 'hip', 'hip_runtime.h')] + staged + ['-o', OUT]
-    subprocess.run(cmd, check=True)
-    with open(stamp, 'w') as f:
-      f.write(digest + '\n')
-    return OUT
-
-
-@pytest.fixture(scope='module')
-def ddsp():
-  import ddsp_amd
-  os.environ.setdefault('DDSP_EMU_CUS', '4')
-  if not os.path.exists(emu_simt.CLANG):
-    pytest.skip('the SIMT emulation builds with the ROCm clang++ (%s), which this machine does not have' % emu_simt.CLANG)
-  lib = ctypes.CDLL(_build())
-  for name, (restype, argtypes) in _lib.SIGNATURES.items():
-    if not hasattr(lib, name):              # (entry points of kernel files this build leaves out)
-      continue
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = restype, argtypes
-  saved = (_lib.load, core._device, core._stream, dict(core._ws_bytes_cache), G.DEV)
-  _lib.load = lambda: lib
-  core._device = lambda: torch.device('cpu')
-  core._stream = lambda: None
-  core._ws_bytes_cache.clear()
-  G.DEV = 'cpu'
-  yield ddsp_amd
-  _lib.load, core._device, core._stream = saved[0], saved[1], saved[2]
-  core._ws_bytes_cache.clear()
-  core._ws_bytes_cache.update(saved[3])
-  G.DEV = saved[4]
-
-
-for _name in dir(G):
-  if _name.startswith('test_') and callable(getattr(G, _name)):
-    globals()[_name] = getattr(G, _name)
+ddsp = emu_simt.ddsp_fixture(G)
+emu_simt.reexport(globals(), G)
 
 # left to the GPU run: the 64 000-sample clips (a thread is a fiber here) and the peak-memory figure (an allocator statistic
 # of the device)

@@ -2,8 +2,10 @@
 
 tests/hip_emu/emu_simt.py compiles the gfx950 kernel sources of ddsp_amd/csrc unchanged for the host (threads of
 a block as fibers, wavefront operations - DPP, readlane, swizzle, MFMA - evaluated when all live lanes have
-arrived); this module points the Python layer of ddsp_amd at that build and at host memory, then runs the very
-test functions of test_gpu_parity.py / test_gpu_parity_general.py whose shapes finish in seconds.  What it
+arrived) into one library, and holds the harness that points the Python layer of ddsp_amd at that build and at
+host memory; this module runs through it the very test functions of test_gpu_parity.py / test_gpu_parity_general.py /
+test_gpu_reference_tests.py whose shapes finish in seconds.  The tests/test_*_emulated.py beside it do the same for
+the GPU modules of the later kernels, each with its own list of cases left to the GPU.  What it
 checks is kernel LOGIC (indexing, LDS layouts, barriers, cross-lane traffic, MFMA fragment layouts, launch
 geometry) and the host glue; it says nothing about performance and does not replace the `-m gpu` run, which is
 the parity gate.  Every kernel exercised here has also passed on the MI355X, which is what pins the emulation
@@ -13,33 +15,13 @@ The product never runs this way: ddsp_amd has no CPU path (test_host_api.test_no
 import os
 
 import pytest
-import torch
 
 import test_gpu_parity as P
 import test_gpu_parity_general as G
 import test_gpu_reference_tests as R
-from ddsp_amd import _lib, core
 from tests.hip_emu import emu_simt
 
-
-@pytest.fixture(scope='module')
-def ddsp():
-  import ddsp_amd
-  os.environ.setdefault('DDSP_EMU_CUS', '4')          # the emulated chip's CU count (persistent kernels size their grid by it)
-  if not os.path.exists(emu_simt.CLANG):
-    pytest.skip('the SIMT emulation builds with the ROCm clang++ (%s), which this machine does not have' % emu_simt.CLANG)
-  lib = emu_simt.load()
-  saved = (_lib.load, core._device, core._stream, dict(core._ws_bytes_cache), P.DEV, G.DEV, R.DEV)
-  _lib.load = lambda: lib
-  core._device = lambda: torch.device('cpu')
-  core._stream = lambda: None
-  core._ws_bytes_cache.clear()
-  P.DEV = G.DEV = R.DEV = 'cpu'
-  yield ddsp_amd
-  _lib.load, core._device, core._stream = saved[0], saved[1], saved[2]
-  core._ws_bytes_cache.clear()
-  core._ws_bytes_cache.update(saved[3])
-  P.DEV, G.DEV, R.DEV = saved[4], saved[5], saved[6]
+ddsp = emu_simt.ddsp_fixture(P, G, R)
 
 
 @pytest.fixture(params=['auto', 'direct'])
@@ -58,13 +40,10 @@ def noise_kernel(request, ddsp):
   ddsp.synths.FilteredNoise.kernel = old
 
 
-# Every test function of the two GPU modules is re-exported under its own name (so its parametrisation comes
+# Every test function of the three GPU modules is re-exported under its own name (so its parametrisation comes
 # along); the cases below are left to the GPU run - minutes each under the emulation (clips of 4 s at batch 32).
 # DDSP_EMU_ALL=1 runs them too (about 17 minutes in all; every one of them passes).
-for _module in (P, G, R):
-  for _name in dir(_module):
-    if _name.startswith('test_') and callable(getattr(_module, _name)):
-      globals()[_name] = getattr(_module, _name)
+emu_simt.reexport(globals(), P, G, R)
 
 SLOW_UNDER_EMULATION = () if os.environ.get('DDSP_EMU_ALL') == '1' else (
     'test_processors_group_dag_construction',                          # 4 x 64 000 samples, 256 bands, a 48 000-tap reverb
