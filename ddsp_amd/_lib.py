@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libddsp_amd.so')
 c_f32p = ctypes.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 c_int, c_uint, c_size_t = ctypes.c_int, ctypes.c_uint, ctypes.c_size_t
 c_u64, c_float, c_voidp = ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
+c_double = ctypes.c_double
 
 # name -> (restype, argtypes); must list every symbol declared in include/ddsp_amd.h
 SIGNATURES = {
@@ -141,6 +142,11 @@ SIGNATURES = {
     'ddsp_unit_convert_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_wasserstein_f32': (c_int, [c_f32p] * 5 + [c_size_t] + [c_int] * 4 + [c_voidp]),
     'ddsp_wasserstein_backward_f32': (c_int, [c_f32p] * 9 + [c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_hmm_log_prob_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_int] + [c_double] * 7 + [c_voidp]),
+    'ddsp_hmm_log_prob_backward_workspace_bytes': (c_size_t, [c_int] * 3),
+    'ddsp_hmm_log_prob_backward_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t, c_size_t, c_int, c_int] + [c_double] * 7 + [c_voidp]),
+    'ddsp_hmm_viterbi_workspace_bytes': (c_size_t, [c_int] * 3),
+    'ddsp_hmm_viterbi_f32': (c_int, [c_f32p] * 3 + [c_voidp, c_size_t, c_size_t, c_int, c_int] + [c_double] * 7 + [c_voidp]),
     'ddsp_fft_convolve_grad_audio_f32': (c_int, [c_f32p] * 3 + [c_int] * 7 + [c_voidp]),
     'ddsp_fft_convolve_grad_ir_f32': (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_voidp]),
     'ddsp_sinc_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_float, c_voidp]),
@@ -187,6 +193,7 @@ WASSERSTEIN_MIDI = 0x1
 CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block stages in LDS (csrc/consistency.hip, wasserstein.hip)
 CONSISTENCY_MAX_POINTS = 256
 CONSISTENCY_MAX_GAUSSIANS = 4096
+HMM_MAX_PITCHES = 1024                  # states of HmmTranscriber a block holds in registers (csrc/hmm.hip)
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
 CONV_ADD_DRY = 0x1

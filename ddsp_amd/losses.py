@@ -478,7 +478,7 @@ class _SpectralLossGeneralFunction(torch.autograd.Function):
 # Consistency losses (ddsp/losses.py:489-578, 689-1076).  csrc/consistency.hip holds the kernels of KDEConsistencyLoss, TWMLoss
 # and core.sinusoidal_to_harmonic, csrc/wasserstein.hip those of WassersteinConsistencyLoss / wasserstein_distance; the thin
 # ones run on mean_difference.  A loss is a sum of up to three 0-dim terms, each the output of a kernel; the terms are added
-# as 0-dim tensors (as SpectralLoss adds its fused and plain parts).
+# as 0-dim tensors (as SpectralLoss adds its fused and plain parts).  csrc/hmm.hip holds the kernels of HmmTranscriber.
 # Not built: EmbeddingLoss, the CREPE classes.
 # --------------------------------------------------------------------------------------
 def amp_loss(amp, amp_target, loss_type='L1', weights=None, log=False, amin=1e-5):
@@ -847,3 +847,138 @@ class WassersteinConsistencyLoss(Loss):
       _sinusoid_frames(('amps_a', 'amps_b'), (amps_a, amps_b), same_last=False)
       loss = core._mean(_wasserstein(freqs_a, freqs_b, amps_a, amps_b, 1.0, _lib.WASSERSTEIN_MIDI), self.weight)
     return loss
+
+
+class _HmmLogProbFunction(torch.autograd.Function):
+  """torch.autograd node of HmmTranscriber's log-likelihood on [rows, steps] tensors (plumbing: both directions are C-ABI
+  calls; the backward call recomputes the forward variables into scratch, so nothing but the inputs is kept)."""
+
+  @staticmethod
+  def forward(ctx, pitch, amps, model):
+    ctx.save_for_backward(pitch, amps)
+    ctx.model = model
+    rows, steps = pitch.shape
+    log_prob = torch.empty((rows,), dtype=torch.float32, device=pitch.device)
+    if rows:
+      rc = _lib.load().ddsp_hmm_log_prob_f32(pitch.data_ptr(), amps.data_ptr(), log_prob.data_ptr(), rows, steps, *model,
+                                             core._stream())
+      _lib.check(rc, 'ddsp_hmm_log_prob_f32')
+    return log_prob
+
+  @staticmethod
+  def backward(ctx, grad_log_prob):
+    pitch, amps = ctx.saved_tensors
+    rows, steps = pitch.shape
+    grad_log_prob = core.tf_float32(grad_log_prob)
+    grads = [torch.empty_like(pitch), torch.empty_like(amps)]
+    if rows:
+      nbytes = core.cached_workspace_bytes('ddsp_hmm_log_prob_backward_workspace_bytes', rows, steps, ctx.model[0])
+      ws = core._default_ws.get(nbytes, pitch.device)
+      rc = _lib.load().ddsp_hmm_log_prob_backward_f32(pitch.data_ptr(), amps.data_ptr(), grad_log_prob.data_ptr(),
+                                                      grads[0].data_ptr(), grads[1].data_ptr(), ws.data_ptr(), ws.numel(), rows,
+                                                      steps, *ctx.model, core._stream())
+      _lib.check(rc, 'ddsp_hmm_log_prob_backward_f32')
+    return grads[0], grads[1], None
+
+
+class HmmTranscriber:
+  """HMM initialized for decoding MIDI from Pitch and Amps (ddsp/losses.py:246-345).
+
+  Discrete hidden states for each midi pitch, f0 observations (in midi).  State 0 is "off" (pitch ~ N(n_pitches / 2,
+  n_pitches), amps ~ N(amps_off_center, amps_off_scale)); state s >= 1 has pitch ~ N(s, midi_std) and amps ~
+  N(amps_on_center, amps_on_scale).  The initial distribution is uniform; a state is held with probability 1 - 1 / avg_length
+  and left for each other state with equal probability.  That matrix is `other` everywhere plus `hold - other` on the
+  diagonal, so a step of the forward algorithm, of its backward pass and of the Viterbi recursion costs O(n_pitches)
+  (csrc/hmm.hip: a block walks a row; nothing of size [n_pitches, n_pitches] or [batch, steps, n_pitches, n_pitches] exists).
+
+  Of tfp.distributions.HiddenMarkovModel, which the reference class derives from, this is log_prob (as `nll`) and
+  posterior_mode (as `predict_midi`).  OUT OF SCOPE: sampling, posterior_marginals as a public method, arbitrary transition or
+  observation models, and the distribution objects the reference keeps as attributes.  Limits of the MI355X path
+  (NotImplementedError): 2 <= n_pitches <= 1024; avg_length >= n_pitches / (n_pitches - 1), i.e. holding a state is at least
+  as likely as any one jump.
+
+  Args:
+    avg_length: Prior over average note length between transitions.
+    midi_std: Prior over f0 variance (in midi) allowed around discrete states.
+    amps_on_center: Center amplitude of the "on" state.
+    amps_on_scale: Variance amplitude of the "on" state.
+    amps_off_center: Center amplitude of the "off" state.
+    amps_off_scale: Variance amplitude of the "off" state.
+    n_timesteps: Number of timesteps in the batch to unroll the HMM.
+    n_pitches: Number of pitches (starting from 0) to use as HMM states.
+    weight: Weighting of the nll loss term.
+  """
+
+  def __init__(self, avg_length=200, midi_std=0.5, amps_on_center=1.5, amps_on_scale=0.5, amps_off_center=0.0,
+               amps_off_scale=0.1, n_timesteps=1000, n_pitches=128, weight=1.0):
+    if not 2 <= n_pitches <= _lib.HMM_MAX_PITCHES:
+      raise NotImplementedError('HmmTranscriber takes 2 <= n_pitches <= {} on the MI355X path, got n_pitches = {}'.format(
+          _lib.HMM_MAX_PITCHES, n_pitches))
+    if min(midi_std, amps_on_scale, amps_off_scale) <= 0.0 or avg_length <= 0.0:
+      raise ValueError('avg_length and the scales must be positive, got avg_length = {}, midi_std = {}, amps_on_scale = {}, '
+                       'amps_off_scale = {}'.format(avg_length, midi_std, amps_on_scale, amps_off_scale))
+    # Transition is heavily peaked around diagonal and uniform otherwise; the rows are renormalised as the reference's are
+    hold = 1.0 - 1.0 / avg_length
+    other = (1.0 - hold) / (n_pitches - 1)
+    total = hold + (n_pitches - 1) * other
+    hold, other = hold / total, other / total
+    if hold < other:
+      raise NotImplementedError('HmmTranscriber needs hold >= other on the MI355X path, i.e. avg_length >= n_pitches / '
+                                '(n_pitches - 1) = {}, got avg_length = {}'.format(n_pitches / (n_pitches - 1.0), avg_length))
+    self.avg_length = avg_length
+    self.midi_std = midi_std
+    self.n_timesteps = n_timesteps
+    self.n_pitches = n_pitches
+    self.weight = weight
+    self._model = (int(n_pitches), hold, other, float(midi_std), float(amps_on_center), float(amps_on_scale),
+                   float(amps_off_center), float(amps_off_scale))
+
+  def __call__(self, pitch, amps):
+    return self.nll(pitch, amps)
+
+  @staticmethod
+  def straight_through(x, x_quant):
+    """Straight through estimation."""
+    return x - (x - x_quant).detach()
+
+  def _observations(self, pitch, amps):
+    """[batch, n_timesteps, 1] each -> contiguous fp32 [batch, n_timesteps]."""
+    pitch, amps = core.tf_float32(pitch), core.tf_float32(amps)
+    if pitch.shape != amps.shape:
+      raise ValueError('pitch and amps must have equal shapes, got {} and {}'.format(tuple(pitch.shape), tuple(amps.shape)))
+    if pitch.dim() != 3 or pitch.shape[2] != 1:
+      raise ValueError('expected [batch, n_timesteps, 1] tensors, got {}'.format(tuple(pitch.shape)))
+    if pitch.shape[1] != self.n_timesteps:
+      raise ValueError('the model is unrolled over n_timesteps = {} steps, got {}'.format(self.n_timesteps, pitch.shape[1]))
+    return pitch.reshape(pitch.shape[:2]), amps.reshape(amps.shape[:2])
+
+  def log_prob(self, pitch, amps):
+    """Log-likelihood of the observations, [batch]; differentiable in pitch and amps."""
+    pitch, amps = self._observations(pitch, amps)
+    if core._needs_grad(pitch, amps):
+      return _HmmLogProbFunction.apply(pitch, amps, self._model)
+    return _HmmLogProbFunction.forward(core._NoCtx(), pitch, amps, self._model)
+
+  def nll(self, pitch, amps, per_example_loss=False):
+    """Negative log-likelihood per a timestep: weight * mean over the batch (0-dim), or [batch] with per_example_loss."""
+    log_prob = self.log_prob(pitch, amps)
+    scale = -float(self.weight) / self.n_timesteps
+    if per_example_loss:
+      return log_prob * scale                 # [batch] numbers: a framework op, as the reference's own `self.weight * loss`
+    return core._mean(log_prob, scale)
+
+  def predict_midi(self, pitch, amps, channel_dim=True, dtype=torch.float32):
+    """Viterbi decode most likely hidden state as the quantized MIDI signal: [batch, n_timesteps, 1], or [batch, n_timesteps]
+    with channel_dim=False.  No gradient flows through it (see straight_through)."""
+    pitch, amps = self._observations(pitch, amps)
+    pitch, amps = pitch.detach(), amps.detach()
+    rows, steps = pitch.shape
+    states = torch.empty((rows, steps), dtype=torch.int32, device=pitch.device)
+    if rows:
+      nbytes = core.cached_workspace_bytes('ddsp_hmm_viterbi_workspace_bytes', rows, steps, self.n_pitches)
+      ws = core._default_ws.get(nbytes, pitch.device)
+      rc = _lib.load().ddsp_hmm_viterbi_f32(pitch.data_ptr(), amps.data_ptr(), states.data_ptr(), ws.data_ptr(), ws.numel(), rows,
+                                            steps, *self._model, core._stream())
+      _lib.check(rc, 'ddsp_hmm_viterbi_f32')
+    q_pitch = states.to(dtype)
+    return q_pitch[:, :, None] if channel_dim else q_pitch

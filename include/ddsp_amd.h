@@ -854,6 +854,41 @@ int ddsp_wasserstein_backward_f32(const float* u_values, const float* v_values, 
                                   float* grad_v_weights, size_t rows, int n_u, int n_v, int p, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * losses.HmmTranscriber (ddsp/losses.py:246-345): csrc/hmm.hip.  The hidden Markov model of the constructor (:275-304) over
+ * n_pitches states: a uniform initial distribution; transitions `hold` on the diagonal and `other` elsewhere (the caller
+ * passes the two numbers, hold + (n_pitches - 1) other = 1); observations (pitch, amps) with independent normal densities -
+ * state 0 ("off"): pitch ~ N(n_pitches / 2, n_pitches), amps ~ N(amps_off_center, amps_off_scale); state s >= 1: pitch ~
+ * N(s, midi_std), amps ~ N(amps_on_center, amps_on_scale).  A block owns a row and walks its steps in order; a step costs
+ * O(n_pitches), and nothing of size [n_pitches, n_pitches] or [rows, steps, n_pitches] is built by the forward-only calls.
+ * No atomics: the same bits on every run and for any subset of the rows.
+ *
+ * ddsp_hmm_log_prob_f32: pitch [rows, steps], amps [rows, steps] -> log_prob [rows], the log-likelihood of the observations
+ *   (tfp's HiddenMarkovModel.log_prob).  The forward variables are kept normalised and their scales are summed in fp64 and
+ *   as integer exponents; observations far from every state (amps = 50, pitch = -300) give a finite value.
+ * ddsp_hmm_log_prob_backward_f32: the same inputs and grad_log_prob [rows] -> grad_pitch, grad_amps [rows, steps] by the
+ *   forward-backward recursion.  It recomputes the forward pass into `workspace`
+ *   (ddsp_hmm_log_prob_backward_workspace_bytes(rows, steps, n_pitches) = rows * steps * n_pitches floats; DDSP_ERR_WORKSPACE
+ *   if smaller); every gradient element is written once.
+ * ddsp_hmm_viterbi_f32: -> states [rows, steps] (int32), the most likely state sequence (posterior_mode); among equals the
+ *   lowest index, as argmax.  `workspace` (ddsp_hmm_viterbi_workspace_bytes: a bit per step and state, an int per step)
+ *   holds the back trace.
+ * Bounds (DDSP_ERR_UNSUPPORTED beyond): 2 <= n_pitches <= 1024; hold >= other > 0.  Any number of steps.
+ */
+int ddsp_hmm_log_prob_f32(const float* pitch, const float* amps, float* log_prob, size_t rows, int steps, int n_pitches,
+                          double hold, double other, double midi_std, double amps_on_center, double amps_on_scale,
+                          double amps_off_center, double amps_off_scale, void* stream);
+size_t ddsp_hmm_log_prob_backward_workspace_bytes(int rows, int steps, int n_pitches);
+int ddsp_hmm_log_prob_backward_f32(const float* pitch, const float* amps, const float* grad_log_prob, float* grad_pitch,
+                                   float* grad_amps, void* workspace, size_t workspace_bytes, size_t rows, int steps,
+                                   int n_pitches, double hold, double other, double midi_std, double amps_on_center,
+                                   double amps_on_scale, double amps_off_center, double amps_off_scale, void* stream);
+size_t ddsp_hmm_viterbi_workspace_bytes(int rows, int steps, int n_pitches);
+int ddsp_hmm_viterbi_f32(const float* pitch, const float* amps, int* states, void* workspace, size_t workspace_bytes,
+                         size_t rows, int steps, int n_pitches, double hold, double other, double midi_std,
+                         double amps_on_center, double amps_on_scale, double amps_off_center, double amps_off_scale,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
