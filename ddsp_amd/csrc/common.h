@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "split_f16.h"      // f32x4
 
 namespace ddsp {
 
@@ -252,17 +253,16 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, FastDiv f, uint32_t& rem
 // A 16-byte global load that is ISSUED where it is written and whose result is first touched at load_settle():
 // a plain load may be sunk by the optimiser to just before its first use (it moved four of them below a block of
 // MFMAs that was there to hide their latency - harmonic_table.hip), a volatile assembly statement may not.
-typedef float ddsp_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void load_issue(ddsp_f32x4& dst, const float4* src) {
+__device__ __forceinline__ void load_issue(f32x4& dst, const float4* src) {
 #if defined(__AMDGCN__)
   __asm__ volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(src));
 #else
   const float4 v = *src;
-  dst = (ddsp_f32x4){v.x, v.y, v.z, v.w};
+  dst = (f32x4){v.x, v.y, v.z, v.w};
 #endif
 }
 // every load issued so far has landed; the four values are ordered behind the wait
-__device__ __forceinline__ void load_settle(ddsp_f32x4& a, ddsp_f32x4& b, ddsp_f32x4& c, ddsp_f32x4& d) {
+__device__ __forceinline__ void load_settle(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
 #if defined(__AMDGCN__)
   __asm__ volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 #else
@@ -280,12 +280,12 @@ __device__ __forceinline__ void load_issue(float& dst, const float* src) {
 #endif
 }
 // The same from a wave-uniform base (scalar register pair) and a 32-bit byte offset per lane: no 64-bit address arithmetic.
-__device__ __forceinline__ void load_issue(ddsp_f32x4& dst, const char* base, unsigned byte_offset) {
+__device__ __forceinline__ void load_issue(f32x4& dst, const char* base, unsigned byte_offset) {
 #if defined(__AMDGCN__)
   __asm__ volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(byte_offset), "s"(base));
 #else
   const float4 v = *reinterpret_cast<const float4*>(base + byte_offset);
-  dst = (ddsp_f32x4){v.x, v.y, v.z, v.w};
+  dst = (f32x4){v.x, v.y, v.z, v.w};
 #endif
 }
 __device__ __forceinline__ void load_issue(float& dst, const char* base, unsigned byte_offset) {
@@ -302,12 +302,12 @@ __device__ __forceinline__ void load_issue(float& dst, const char* base, unsigne
 // (profiles/r03u_*: stale bases, wrong samples that move from run to run).  tests/test_isa_guards.py checks every pinned
 // load of every instance for this.
 template <int IMM>
-__device__ __forceinline__ void load_issue_spaced(ddsp_f32x4& dst, const char* base, unsigned byte_offset) {
+__device__ __forceinline__ void load_issue_spaced(f32x4& dst, const char* base, unsigned byte_offset) {
 #if defined(__AMDGCN__)
   __asm__ volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(byte_offset), "s"(base), "n"(IMM));
 #else
   const float4 v = *reinterpret_cast<const float4*>(base + byte_offset + IMM);
-  dst = (ddsp_f32x4){v.x, v.y, v.z, v.w};
+  dst = (f32x4){v.x, v.y, v.z, v.w};
 #endif
 }
 template <int IMM>
@@ -319,7 +319,7 @@ __device__ __forceinline__ void load_issue_spaced(float& dst, const char* base, 
 #endif
 }
 // every load this wavefront has issued has landed; the listed values are ordered behind the wait
-__device__ __forceinline__ void loads_landed(ddsp_f32x4& a, float& b, float& c) {
+__device__ __forceinline__ void loads_landed(f32x4& a, float& b, float& c) {
 #if defined(__AMDGCN__)
   __asm__ volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c));
 #else

@@ -42,6 +42,7 @@
 #include "../../include/ddsp_amd.h"
 #include "common.h"
 #include "consistency_common.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace consistency {
@@ -565,7 +566,6 @@ __global__ __launch_bounds__(kThreads) void convert_backward_kernel(const float*
   out[i] = g[i] * d;
 }
 
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
 static unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 static bool rows_ok(size_t rows) { return rows > 0 && rows <= (size_t)0x7fffffff; }
 

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace features {
@@ -70,6 +71,7 @@ static inline float db_floor_power(float range_db) { return (float)pow(10.0, -(d
 }  // namespace features
 }  // namespace ddsp
 
+using namespace ddsp;
 using namespace ddsp::features;
 
 extern "C" int ddsp_frame_energy_f32(const float* audio, float* out, int B, int N, int frame_size, int hop, int pad_left, int n_frames,
@@ -84,7 +86,7 @@ extern "C" int ddsp_frame_energy_f32(const float* audio, float* out, int B, int 
   const long blocks = (p.rows + kFramesPerBlock - 1) / kFramesPerBlock;
   if (blocks > 0x7fffffffL) return DDSP_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(frame_energy_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, audio, out, p);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_db_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream) {
@@ -94,5 +96,5 @@ extern "C" int ddsp_db_convert_f32(const float* in, float* out, size_t n, int op
   const size_t blocks = (n + kThreads - 1) / kThreads;
   hipLaunchKernelGGL(db_convert_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kThreads), 0, (hipStream_t)stream, in,
                      out, n, op, p0, p1, op <= DDSP_DB_AMPLITUDE_TO_DB ? db_floor_power(p1) : 0.0f);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }

@@ -8,15 +8,21 @@
 // (tap set chosen by the frame of the INPUT sample; oracle test
 // test_fft_convolve_equals_direct_time_varying_fir), which is what is evaluated here:
 // no FFT, no [B,F,fft_size] complex intermediates in HBM.
+//
+// What lives here: FilteredNoise's controls, IR designs, FIRs, noise generator and backward pass, and ddsp_add_f32 (see
+// add_kernel for why).  The split-fp16 operand is split_f16.h's, the launch helpers launch.h's; resample and exp_sigmoid are
+// in general.hip and fir_grad.hip.
 #include <hip/hip_ext.h>
 #include <cstdlib>
 #include "common.h"
+#include "split_f16.h"
 #include "noise_ir65.h"
 #include "filtered_noise_mfma.h"
 #include "filtered_noise_general.h"
 #include "noise_ir_geom.h"
 #include "profile.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -239,12 +245,14 @@ __device__ __forceinline__ int fir_x_addr(int ip) {      // ip = i - (z0 - 128),
   return (c & 3) * kFirPlane + ((c >> 2) << 2) + (ip & 3);
 }
 
+// sixteen consecutive samples from an x tile of four chunk planes, PLANE dwords each
+template <int PLANE>
 __device__ __forceinline__ void fir_load16(const float* s_x, int ip, float (&v)[16]) {
   const int chunk = ip >> 2;                               // ip is a multiple of 16
 #pragma unroll
   for (int c4 = 0; c4 < 4; ++c4) {
     const int c = chunk + c4;
-    const float4 t = *reinterpret_cast<const float4*>(&s_x[(c & 3) * kFirPlane + ((c >> 2) << 2)]);
+    const float4 t = *reinterpret_cast<const float4*>(&s_x[(c & 3) * PLANE + ((c >> 2) << 2)]);
     v[4 * c4] = t.x; v[4 * c4 + 1] = t.y; v[4 * c4 + 2] = t.z; v[4 * c4 + 3] = t.w;
   }
 }
@@ -256,7 +264,7 @@ __device__ __forceinline__ void fir_tap_block(const float* s_x, const float* s_h
   // frame(i0) and frame(i0-16) as tap-row indices (row 0 = frame J0-2); irel = i0 - z0 >= -112
   const int rowA = (irel + 128) >> 6;
   const int rowB = (irel + 112) >> 6;
-  fir_load16(s_x, irel + 128 - 16, lo);
+  fir_load16<kFirPlane>(s_x, irel + 128 - 16, lo);
   float ta[16], tb[16];
 #pragma unroll
   for (int c4 = 0; c4 < 4; ++c4) {
@@ -337,7 +345,7 @@ __global__ __launch_bounds__(64 * kFirWaves, 4) void tv_fir128_kernel(
   for (int r = 0; r < kFirR; ++r) acc[r] = 0.0f;
 
   float xa[16], xb[16];                   // x[i0 .. i0+15] and x[i0-16 .. i0-1], roles alternate
-  fir_load16(s_x, mrel + 128, xa);                         // i0 - (z0 - 128) at k0 = 0
+  fir_load16<kFirPlane>(s_x, mrel + 128, xa);                         // i0 - (z0 - 128) at k0 = 0
 #pragma unroll 1
   for (int kb = 0; kb < 8; kb += 2) {                      // two tap blocks per trip: ping-pong
     fir_tap_block(s_x, s_h, mrel - 16 * kb, 16 * kb, acc, xa, xb);
@@ -378,15 +386,6 @@ __device__ __forceinline__ int fn_out_addr(int e) {
   return (e & ~15) + ((((e >> 2) ^ (e >> 6)) & 3) << 2) + (e & 3);
 }
 
-__device__ __forceinline__ void fn_load16(const float* s_x, int ip, float (&v)[16]) {
-  const int chunk = ip >> 2;
-#pragma unroll
-  for (int c4 = 0; c4 < 4; ++c4) {
-    const int c = chunk + c4;
-    const float4 t = *reinterpret_cast<const float4*>(&s_x[(c & 3) * kFnPlane + ((c >> 2) << 2)]);
-    v[4 * c4] = t.x; v[4 * c4 + 1] = t.y; v[4 * c4 + 2] = t.z; v[4 * c4 + 3] = t.w;
-  }
-}
 // irel = i0 - z0 (multiple of 16, >= -112); rel0 = (z0 - 128) - f_first*fs >= 0; rows are frames
 // relative to f_first.  (x + 0.5) * inv_fs floors exactly for the magnitudes involved (< 2^13).
 __device__ __forceinline__ void fn_tap_block(const float* s_x, const float* s_h, int irel, int k0,
@@ -394,7 +393,7 @@ __device__ __forceinline__ void fn_tap_block(const float* s_x, const float* s_h,
                                              float (&lo)[16], int rel0, float inv_fs) {
   const int rowA = (int)(((float)(irel + 128 + rel0) + 0.5f) * inv_fs);   // frame(i0)    - f_first
   const int rowB = (int)(((float)(irel + 112 + rel0) + 0.5f) * inv_fs);   // frame(i0-16) - f_first
-  fn_load16(s_x, irel + 128 - 16, lo);
+  fir_load16<kFnPlane>(s_x, irel + 128 - 16, lo);
   // two passes so that the taps of frame(i0) and of frame(i0-16) are never live together
   // (the 8-wavefront variant has 80 VGPRs: acc + hi + lo + one set of 16 taps = 64)
   {
@@ -434,16 +433,14 @@ struct FusedNoiseArgs {
   int bits23;
 };
 
-typedef _Float16 fn_f16x8 __attribute__((ext_vector_type(8)));
-typedef float fn_f32x4 __attribute__((ext_vector_type(4)));
-constexpr float kFnLoScale = 2048.0f;     // x = hi + lo / 2048 in two fp16 numbers (as harmonic_table.hip)
-
-__device__ __forceinline__ void fn_split8(const float (&v)[8], fn_f16x8& hi, fn_f16x8& lo) {
+// split_f16.h's split8 with hi[e] written before lo[e] is computed.  The two forms mean the same and do not compile to the same
+// schedule: noise_fused65_kernel keeps the one it was measured with.
+__device__ __forceinline__ void fn_split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const _Float16 h = (_Float16)v[e];
     hi[e] = h;
-    lo[e] = (_Float16)((v[e] - (float)h) * kFnLoScale);
+    lo[e] = (_Float16)((v[e] - (float)h) * kLoScale);
   }
 }
 
@@ -487,7 +484,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 6 : 3)) void noise_fused65_kern
   // (i = lane & 15, g = lane >> 4): coefficient of tap n = 16 mt + i and bin 2 k' (+ 1), k' = 8 g + e.
   constexpr int kMt = (NW == 8) ? 1 : 2;
   const int mt0 = (NW == 8) ? (wave >> 2) : 0;
-  fn_f16x8 ae_hi[kMt], ae_lo[kMt], ao_hi[kMt], ao_lo[kMt];
+  f16x8 ae_hi[kMt], ae_lo[kMt], ao_hi[kMt], ao_lo[kMt];
   {
 #pragma unroll
     for (int q = 0; q < kMt; ++q) {
@@ -568,20 +565,20 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 6 : 3)) void noise_fused65_kern
     float ve[8], vo[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { ve[e] = y[2 * e]; vo[e] = y[2 * e + 1]; }
-    fn_f16x8 be_hi, be_lo, bo_hi, bo_lo;
+    f16x8 be_hi, be_lo, bo_hi, bo_lo;
     fn_split8(ve, be_hi, be_lo);
     fn_split8(vo, bo_hi, bo_lo);
     float* __restrict__ hrow = s_h + rrow * kTapStride;
 #pragma unroll
     for (int q = 0; q < kMt; ++q) {
-      const fn_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-      fn_f32x4 ea = __builtin_amdgcn_mfma_f32_16x16x32_f16(ae_hi[q], be_hi, zero, 0, 0, 0);
-      fn_f32x4 oa = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao_hi[q], bo_hi, zero, 0, 0, 0);
-      fn_f32x4 ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(ae_hi[q], be_lo, zero, 0, 0, 0);
-      fn_f32x4 ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao_hi[q], bo_lo, zero, 0, 0, 0);
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      f32x4 ea = __builtin_amdgcn_mfma_f32_16x16x32_f16(ae_hi[q], be_hi, zero, 0, 0, 0);
+      f32x4 oa = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao_hi[q], bo_hi, zero, 0, 0, 0);
+      f32x4 ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(ae_hi[q], be_lo, zero, 0, 0, 0);
+      f32x4 ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao_hi[q], bo_lo, zero, 0, 0, 0);
       ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(ae_lo[q], be_hi, ex, 0, 0, 0);
       ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao_lo[q], bo_hi, ox, 0, 0, 0);
-      const fn_f32x4 ev = ea + ex * (1.0f / kFnLoScale), ov = oa + ox * (1.0f / kFnLoScale);
+      const f32x4 ev = combine(ea, ex), ov = combine(oa, ox);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = 16 * (mt0 + q) + 4 * mg + r;                    // 0 .. 31
@@ -626,7 +623,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 6 : 3)) void noise_fused65_kern
   if (mrel < kFnTile) {
     const int kb0 = (NW == 8) ? 4 * half : 0;
     float xa[16], xb[16];
-    fn_load16(s_u, mrel + 128 - 16 * kb0, xa);
+    fir_load16<kFnPlane>(s_u, mrel + 128 - 16 * kb0, xa);
 #pragma unroll 1
     for (int kb = kb0; kb < kb0 + (NW == 8 ? 4 : 8); kb += 2) {
       fn_tap_block(s_u, s_h, mrel - 16 * kb, 16 * kb, acc, xa, xb, rel0, p.inv_fs);
@@ -685,6 +682,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 6 : 3)) void noise_fused65_kern
 #undef DDSP_STAMP
 }
 
+// processors.Add on the synths' outputs.  It stays in this file: its launch is bracketed by a ProfileScope and it moves float4s,
+// and general.hip, where its siblings live, is also compiled for the host against a stand-in runtime that has neither.
 __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a,
                                                   const float* __restrict__ b,
                                                   float* __restrict__ out, size_t n) {
@@ -701,29 +700,12 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a,
     out[i] = a[i] + b[i];
 }
 
-__global__ __launch_bounds__(256) void exp_sigmoid_kernel(const float* __restrict__ in,
-                                                          float* __restrict__ out, size_t n,
-                                                          float log_exponent, float max_value,
-                                                          float threshold) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    out[i] = exp_sigmoid(in[i], log_exponent, max_value, threshold);
-}
-
 }  // namespace ddsp
 
 // =====================================================================================
 // C ABI
 // =====================================================================================
 using namespace ddsp;
-
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
-static inline unsigned grid_for(size_t n, unsigned cap = 256 * 8) {
-  size_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-constexpr size_t kMaxDynLds = 64 * 1024;
-
-extern "C" const char* ddsp_version(void) { return "ddsp_amd 0.1.0 gfx950"; }
 
 extern "C" int ddsp_fir_size(int M, int window_size) {
   if (M < 2) return DDSP_ERR_BAD_SHAPE;
@@ -737,7 +719,7 @@ extern "C" int ddsp_filtered_noise_controls_f32(const float* magnitudes, float* 
   if (B <= 0 || F <= 0 || M <= 0) return DDSP_ERR_BAD_SHAPE;
   const size_t n = (size_t)B * F * M;
   ProfileScope prof(kNoiseControls, (hipStream_t)stream);
-  hipLaunchKernelGGL(noise_controls_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(noise_controls_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream,
                      magnitudes, ctl, n, initial_bias,
                      (flags & DDSP_NOISE_SCALE_EXP_SIGMOID) ? 1 : 0);
   return check_launch();
@@ -1204,67 +1186,7 @@ extern "C" int ddsp_add_f32(const float* a, const float* b, float* out, size_t n
   if (n == 0) return DDSP_OK;
   if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) return DDSP_ERR_UNSUPPORTED;
   ProfileScope prof(kAdd, (hipStream_t)stream);
-  hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b,
+  hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4 + 1, 256 * 8)), dim3(256), 0, (hipStream_t)stream, a, b,
                      out, n);
-  return check_launch();
-}
-
-extern "C" int ddsp_exp_sigmoid_f32(const float* in, float* out, size_t n, float exponent,
-                                    float max_value, float threshold, void* stream) {
-  if (!in || !out) return DDSP_ERR_NULL_POINTER;
-  if (n == 0) return DDSP_OK;
-  ProfileScope prof(kExpSigmoid, (hipStream_t)stream);
-  hipLaunchKernelGGL(exp_sigmoid_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, in,
-                     out, n, logf(exponent), max_value, threshold);
-  return check_launch();
-}
-
-// =====================================================================================
-// Stand-alone frame-rate -> audio-rate resampling (core.resample 'linear' / 'window',
-// ddsp/core.py:573-714) for callers that want the envelopes themselves.  The synth kernels
-// never materialise these [B,N,C] tensors; this is an HBM-write-bound elementwise kernel.
-// =====================================================================================
-namespace ddsp {
-// out[b,t,c] = x[b,lo,c]*(1-w) + x[b,hi,c]*w with
-//   'linear' (legacy bilinear, align_corners=False): pos = t*fl32(F/N), lo=floor, hi=min(ceil,F-1),
-//             w = pos-lo, evaluated as top + (bottom-top)*w exactly like TF;
-//   'window' (upsample_with_windows, add_endpoint=True): j=t/hop, r=t%hop, hi=min(j+1,F-1),
-//             w = Hann(2*hop)[r] = 0.5-0.5*cos(pi*r/hop), out = x[j]*(1-w) + x[hi]*w.
-__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x,
-                                                       float* __restrict__ out, int F, int N, int C,
-                                                       int window, float scale, int hop) {
-  const int b = blockIdx.y;
-  const size_t total = (size_t)N * C;
-  const float* __restrict__ xb = x + (size_t)b * F * C;
-  float* __restrict__ ob = out + (size_t)b * total;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int t = (int)(i / C), c = (int)(i - (size_t)t * C);
-    if (window) {
-      const int j = t / hop, r = t - j * hop;
-      const int hi = min(j + 1, F - 1);
-      const float w = 0.5f - 0.5f * cospif((float)r / (float)hop);
-      ob[i] = xb[(size_t)j * C + c] * (1.0f - w) + xb[(size_t)hi * C + c] * w;
-    } else {
-      // every step individually rounded (no FMA contraction of t*scale - lo: found on the MI355X in round 1)
-      const float pos = rn_mul((float)t, scale);
-      const float lo = floorf(pos);
-      const int lo_i = (int)lo, hi_i = min((int)ceilf(pos), F - 1);
-      const float top = xb[(size_t)lo_i * C + c], bottom = xb[(size_t)hi_i * C + c];
-      ob[i] = rn_add(top, rn_mul(rn_sub(bottom, top), rn_sub(pos, lo)));
-    }
-  }
-}
-}  // namespace ddsp
-
-extern "C" int ddsp_resample_f32(const float* x, float* out, int B, int F, int N, int C, int window,
-                                 void* stream) {
-  if (!x || !out) return DDSP_ERR_NULL_POINTER;
-  if (B <= 0 || F <= 0 || N <= 0 || C <= 0 || B > 65535) return DDSP_ERR_BAD_SHAPE;
-  if (window && (N % F != 0)) return DDSP_ERR_BAD_SHAPE;
-  const float scale = (float)F / (float)N;            // fp32, as TF computes it
-  const size_t total = (size_t)N * C;
-  const dim3 grid(grid_for(total, 2048), (unsigned)B);
-  hipLaunchKernelGGL(ddsp::resample_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, out, F, N, C,
-                     window, scale, window ? N / F : 1);
   return check_launch();
 }

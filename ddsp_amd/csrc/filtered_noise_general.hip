@@ -44,33 +44,13 @@
 #include <vector>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "split_f16.h"
 #include "noise_ir_geom.h"
 #include "profile.h"
 #include "filtered_noise_general.h"
+#include "launch.h"
 
 namespace ddsp {
-
-typedef _Float16 gf_f16x8 __attribute__((ext_vector_type(8)));
-typedef float gf_f32x4 __attribute__((ext_vector_type(4)));
-struct __attribute__((packed, aligned(4))) GfU4 { uint32_t x, y, z, w; };       // 16 bytes from a 4-byte aligned address
-constexpr float kGfLoScale = 2048.0f;
-
-__device__ __forceinline__ void gf_split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)((v - (float)hi) * kGfLoScale);
-}
-__device__ __forceinline__ uint32_t gf_pack(_Float16 a, _Float16 b) {
-  return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-}
-__device__ __forceinline__ void gf_split8(const float (&v)[8], gf_f16x8& hi, gf_f16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    _Float16 h, l;
-    gf_split(v[e], h, l);
-    hi[e] = h;
-    lo[e] = l;
-  }
-}
 
 // =====================================================================================================================
 // IR design
@@ -102,16 +82,15 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
   constexpr int kNtg = GiChunk<KS>::kNtg, kChunk = kNtg * kTile, kPre = (kChunk + 64 * kGiWaves - 1) / (64 * kGiWaves);
   constexpr int kBuf = kPre * 64 * kGiWaves;                            // an LDS buffer: a chunk, rounded up to whole rounds of the copy
   // (the matrix is padded to whole chunks on the host: no bounds in the copies, so that `pre` stays in registers)
-  typedef uint32_t gi_u32x4 __attribute__((ext_vector_type(4)));      // (an array of HIP's uint4 - a struct of unions - stays in scratch)
-  gi_u32x4 pre[kPre];
+  u32x4 pre[kPre];
 #define DDSP_GI_FETCH(nt0)                                                       \
   {                                                                              \
-    const gi_u32x4* src_ = reinterpret_cast<const gi_u32x4*>(cm) + (size_t)(nt0) * kTile + tid; \
+    const u32x4* src_ = reinterpret_cast<const u32x4*>(cm) + (size_t)(nt0) * kTile + tid; \
     _Pragma("unroll") for (int j = 0; j < kPre; ++j) pre[j] = src_[64 * kGiWaves * j]; \
   }
 #define DDSP_GI_STASH(buf)                                                       \
   {                                                                              \
-    gi_u32x4* dst_ = reinterpret_cast<gi_u32x4*>(buf) + tid;                     \
+    u32x4* dst_ = reinterpret_cast<u32x4*>(buf) + tid;                     \
     _Pragma("unroll") for (int j = 0; j < kPre; ++j) dst_[64 * kGiWaves * j] = pre[j]; \
   }
   DDSP_GI_FETCH(0);
@@ -165,7 +144,7 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
   }
   __syncthreads();
   // this wavefront's 16 rows as A-fragments: lane (i, g) holds bins 32 ks + 8 g .. + 7 of row i
-  gf_f16x8 ah[KS], al[KS];
+  f16x8 ah[KS], al[KS];
   // Magnitudes that are not squashed by exp_sigmoid (core.frequency_impulse_response on the caller's own: any scale) are brought
   // to [1/2, 1) by the power of two of the largest among this wavefront's sixteen rows before the fp16 hi / lo split; the
   // epilogue takes it back (the design is linear)
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = ldexpf(v[e], -a_exp);
       }
-      gf_split8(v, ah[ks], al[ks]);
+      split8(v, ah[ks], al[ks]);
     }
   }
   __syncthreads();                          // (the fragments are in registers: the space is the chunk buffers' from here on)
@@ -207,12 +186,12 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
     constexpr int kG = kNtg < 4 ? kNtg : 4;
 #pragma unroll 1
     for (int t0 = 0; t0 < n_chunk; t0 += kG) {
-      gf_f32x4 acc[kG], acc_hl[kG], acc_lh[kG];
+      f32x4 acc[kG], acc_hl[kG], acc_lh[kG];
 #pragma unroll
       for (int u = 0; u < kG; ++u) {
-        acc[u] = (gf_f32x4){0.f, 0.f, 0.f, 0.f};
-        acc_hl[u] = (gf_f32x4){0.f, 0.f, 0.f, 0.f};
-        acc_lh[u] = (gf_f32x4){0.f, 0.f, 0.f, 0.f};
+        acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        acc_hl[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        acc_lh[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -220,8 +199,8 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
         for (int u = 0; u < kG; ++u) {
           // (tiles past the chunk's end multiply whatever the buffer holds: inside the buffer, never stored)
           const int t = t0 + u < kNtg ? t0 + u : kNtg - 1;
-          const gf_f16x8 bh = __builtin_bit_cast(gf_f16x8, buf[((t * KS + ks) * 2 + 0) * 64 + lane]);
-          const gf_f16x8 bl = __builtin_bit_cast(gf_f16x8, buf[((t * KS + ks) * 2 + 1) * 64 + lane]);
+          const f16x8 bh = __builtin_bit_cast(f16x8, buf[((t * KS + ks) * 2 + 0) * 64 + lane]);
+          const f16x8 bl = __builtin_bit_cast(f16x8, buf[((t * KS + ks) * 2 + 1) * 64 + lane]);
           acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], bh, acc[u], 0, 0, 0);
           acc_hl[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], bl, acc_hl[u], 0, 0, 0);
           acc_lh[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ks], bh, acc_lh[u], 0, 0, 0);
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(64 * kGiWaves) void noise_ir_gemm_kernel(const floa
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const long rr = row0 + 4 * g + r;
-            const float v = ldexpf(acc[u][r] + (acc_hl[u][r] + acc_lh[u][r]) * (1.0f / kGfLoScale), a_exp);
+            const float v = ldexpf(combine(acc[u][r], acc_hl[u][r] + acc_lh[u][r]), a_exp);
             if (rr < rows) ir[rr * L + col] = v;
           }
         }
@@ -259,6 +238,32 @@ static float gi_f16_value(unsigned short b) {
   _Float16 h;
   memcpy(&h, &b, 2);
   return (float)h;
+}
+// x as the bit patterns of its fp16 hi and lo parts: split_f16.h's split(), on the host
+struct GiHalves { unsigned short hi, lo; };
+static GiHalves gi_split_bits(float x) {
+  const unsigned short hb = gi_f16_bits(x);
+  return {hb, gi_f16_bits((x - gi_f16_value(hb)) * kLoScale)};
+}
+// A matrix B[k][n], element (k, n) = at(k, n), as MFMA B-fragments [tile of 16 n][k-step of 32 k][hi / lo][lane] of 16 bytes:
+// lane holds k = 32 ks + 8 (lane >> 4) + e, n = 16 nt + (lane & 15).  `words` dwords, zeros behind the fragments.
+template <class At>
+static std::vector<uint32_t> gi_frags(int n_tiles, int k_steps, size_t words, At at) {
+  std::vector<uint32_t> f(words, 0u);
+  for (int nt = 0; nt < n_tiles; ++nt)
+    for (int ks = 0; ks < k_steps; ++ks)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int d = 0; d < 4; ++d) {
+          uint32_t hi2 = 0, lo2 = 0;
+          for (int h = 0; h < 2; ++h) {
+            const GiHalves x = gi_split_bits(at(32 * ks + 8 * (lane >> 4) + 2 * d + h, 16 * nt + (lane & 15)));
+            hi2 |= (uint32_t)x.hi << (16 * h);
+            lo2 |= (uint32_t)x.lo << (16 * h);
+          }
+          f[((((size_t)nt * k_steps + ks) * 2 + 0) * 64 + lane) * 4 + d] = hi2;
+          f[((((size_t)nt * k_steps + ks) * 2 + 1) * 64 + lane) * 4 + d] = lo2;
+        }
+  return f;
 }
 struct GiMatrix {
   uint4* dev = nullptr; int NT = 0, KS = 0;
@@ -307,23 +312,8 @@ static const GiMatrix* gi_matrix(int M, int window_size) {
   const size_t chunk_u4 = (size_t)ntg * m.KS * 128;
   const size_t round_u4 = (chunk_u4 + 64 * kGiWaves - 1) / (64 * kGiWaves) * (64 * kGiWaves);
   const size_t n_chunks = ((size_t)m.NT + ntg - 1) / ntg;
-  std::vector<uint32_t> frags(((n_chunks - 1) * chunk_u4 + round_u4) * 4, 0u);
-  for (int nt = 0; nt < m.NT; ++nt)
-    for (int ks = 0; ks < m.KS; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int d = 0; d < 4; ++d) {
-          uint32_t hi2 = 0, lo2 = 0;
-          for (int h = 0; h < 2; ++h) {
-            const int k = 32 * ks + 8 * (lane >> 4) + 2 * d + h, col = 16 * nt + (lane & 15);
-            const float x = c[(size_t)k * m.NT * 16 + col];
-            const unsigned short hb = gi_f16_bits(x);
-            const unsigned short lb = gi_f16_bits((x - gi_f16_value(hb)) * kGfLoScale);
-            hi2 |= (uint32_t)hb << (16 * h);
-            lo2 |= (uint32_t)lb << (16 * h);
-          }
-          frags[((((size_t)nt * m.KS + ks) * 2 + 0) * 64 + lane) * 4 + d] = hi2;
-          frags[((((size_t)nt * m.KS + ks) * 2 + 1) * 64 + lane) * 4 + d] = lo2;
-        }
+  const std::vector<uint32_t> frags = gi_frags(m.NT, m.KS, ((n_chunks - 1) * chunk_u4 + round_u4) * 4,
+                                               [&](int k, int col) { return c[(size_t)k * m.NT * 16 + col]; });
   if (hipMalloc((void**)&m.dev, frags.size() * 4) != hipSuccess) return nullptr;
   if (hipMemcpy(m.dev, frags.data(), frags.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(m.dev);
@@ -355,23 +345,9 @@ static const GiMatrix* gi_matrix(int M, int window_size) {
     m.NTu = ((int)uniq.size() + 15) / 16;
     if (m.NTu < 1) m.NTu = 1;
     dest.resize((size_t)m.NTu * 16, 0xFFFFFFFFu);
-    std::vector<uint32_t> fu((size_t)m.NTu * m.KS * 2 * 64 * 4, 0u);
-    for (int nt = 0; nt < m.NTu; ++nt)
-      for (int ks = 0; ks < m.KS; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int d = 0; d < 4; ++d) {
-            uint32_t hi2 = 0, lo2 = 0;
-            for (int h = 0; h < 2; ++h) {
-              const int k = 32 * ks + 8 * (lane >> 4) + 2 * d + h, u = 16 * nt + (lane & 15);
-              const float x = u < (int)uniq.size() ? c[(size_t)k * ld + uniq[u]] : 0.0f;
-              const unsigned short hb = gi_f16_bits(x);
-              const unsigned short lb = gi_f16_bits((x - gi_f16_value(hb)) * kGfLoScale);
-              hi2 |= (uint32_t)hb << (16 * h);
-              lo2 |= (uint32_t)lb << (16 * h);
-            }
-            fu[((((size_t)nt * m.KS + ks) * 2 + 0) * 64 + lane) * 4 + d] = hi2;
-            fu[((((size_t)nt * m.KS + ks) * 2 + 1) * 64 + lane) * 4 + d] = lo2;
-          }
+    const std::vector<uint32_t> fu = gi_frags(m.NTu, m.KS, (size_t)m.NTu * m.KS * 2 * 64 * 4, [&](int k, int u) {
+      return u < (int)uniq.size() ? c[(size_t)k * ld + uniq[u]] : 0.0f;
+    });
     if (hipMalloc((void**)&m.dev_u, fu.size() * 4) != hipSuccess || hipMalloc((void**)&m.dest, dest.size() * 4) != hipSuccess ||
         hipMemcpy(m.dev_u, fu.data(), fu.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(m.dest, dest.data(), dest.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
@@ -385,23 +361,9 @@ static const GiMatrix* gi_matrix(int M, int window_size) {
     const int ld = m.NT * 16;
     m.KSt = (g.L + 31) / 32;
     m.NTb = (M + 15) / 16;
-    std::vector<uint32_t> ft((size_t)m.NTb * m.KSt * 2 * 64 * 4, 0u);
-    for (int nb = 0; nb < m.NTb; ++nb)
-      for (int ks = 0; ks < m.KSt; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int d = 0; d < 4; ++d) {
-            uint32_t hi2 = 0, lo2 = 0;
-            for (int h = 0; h < 2; ++h) {
-              const int t = 32 * ks + 8 * (lane >> 4) + 2 * d + h, band = 16 * nb + (lane & 15);
-              const float x = (t < g.L && band < M) ? c[(size_t)band * ld + t] : 0.0f;
-              const unsigned short hb = gi_f16_bits(x);
-              const unsigned short lb = gi_f16_bits((x - gi_f16_value(hb)) * kGfLoScale);
-              hi2 |= (uint32_t)hb << (16 * h);
-              lo2 |= (uint32_t)lb << (16 * h);
-            }
-            ft[((((size_t)nb * m.KSt + ks) * 2 + 0) * 64 + lane) * 4 + d] = hi2;
-            ft[((((size_t)nb * m.KSt + ks) * 2 + 1) * 64 + lane) * 4 + d] = lo2;
-          }
+    const std::vector<uint32_t> ft = gi_frags(m.NTb, m.KSt, (size_t)m.NTb * m.KSt * 2 * 64 * 4, [&](int t, int band) {
+      return (t < g.L && band < M) ? c[(size_t)band * ld + t] : 0.0f;
+    });
     if (hipMalloc((void**)&m.dev_t, ft.size() * 4) != hipSuccess ||
         hipMemcpy(m.dev_t, ft.data(), ft.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipFree(m.dev);                                    // (every buffer made so far: ADVICE r4)
@@ -456,7 +418,7 @@ int launch_noise_ir_gemm(const float* mag, float* ctl_out, float* ir, long rows,
     case 9: gi_launch<9>(mag, ctl_out, ir, m, rows, M, L, bias, scale, st); break;
     default: return DDSP_ERR_UNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 // =====================================================================================================================
@@ -575,9 +537,8 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
   // the constant matrix (its fragments straight from L2 into registers, requested before anything else) with the row
   // groups, and writes the products - split again - where the FIR's B-fragments are read from.
   if constexpr (KS > 0) {
-    typedef uint32_t gi_u32x4 __attribute__((ext_vector_type(4)));
     const int NTt = p.NTu;                                    // tiles of 16 distinct columns
-    gi_u32x4 bfr[NPW][KS][2];
+    u32x4 bfr[NPW][KS][2];
     uint32_t col_dest[NPW];
 #pragma unroll
     for (int n = 0; n < NPW; ++n) {
@@ -585,7 +546,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       const int nt = wave + 8 * n;
       if (nt < NTt) {
         col_dest[n] = p.dest[16 * nt + (lane & 15)];
-        const gi_u32x4* src = reinterpret_cast<const gi_u32x4*>(p.cm) + (size_t)nt * KS * 128 + lane;
+        const u32x4* src = reinterpret_cast<const u32x4*>(p.cm) + (size_t)nt * KS * 128 + lane;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           bfr[n][ks][0] = src[(2 * ks + 0) * 64];
@@ -618,10 +579,10 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
         if (ctl && f_lo + r >= own_lo && f_lo + r < own_hi) reinterpret_cast<float4*>(ctl)[k] = q;
         _Float16 h[4], l[4];
         if (h_exp) { q.x = ldexpf(q.x, -h_exp); q.y = ldexpf(q.y, -h_exp); q.z = ldexpf(q.z, -h_exp); q.w = ldexpf(q.w, -h_exp); }
-        gf_split(q.x, h[0], l[0]); gf_split(q.y, h[1], l[1]); gf_split(q.z, h[2], l[2]); gf_split(q.w, h[3], l[3]);
+        split(q.x, h[0], l[0]); split(q.y, h[1], l[1]); split(q.z, h[2], l[2]); split(q.w, h[3], l[3]);
         uint8_t* dst = smem + (r * SA + 4 * c4) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(gf_pack(h[0], h[1]), gf_pack(h[2], h[3]));
-        *reinterpret_cast<uint2*>(dst + a_plane) = make_uint2(gf_pack(l[0], l[1]), gf_pack(l[2], l[3]));
+        *reinterpret_cast<uint2*>(dst) = make_uint2(pack(h[0], h[1]), pack(h[2], h[3]));
+        *reinterpret_cast<uint2*>(dst + a_plane) = make_uint2(pack(l[0], l[1]), pack(l[2], l[3]));
       }
     } else {
       for (int k = tid; k < rows_valid * p.M; k += nthr) {
@@ -629,7 +590,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
         const int r = k / p.M, c = k - r * p.M;
         if (ctl && f_lo + r >= own_lo && f_lo + r < own_hi) ctl[k] = q;
         _Float16 h, l;
-        gf_split(ldexpf(q, -h_exp), h, l);
+        split(ldexpf(q, -h_exp), h, l);
         *reinterpret_cast<_Float16*>(smem + (r * SA + c) * 2) = h;
         *reinterpret_cast<_Float16*>(smem + (r * SA + c) * 2 + a_plane) = l;
       }
@@ -659,13 +620,13 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
         if (nt >= NTt) continue;                               // (wave-uniform)
 #pragma unroll 1
         for (int rg = 0; rg < p.row_groups; ++rg) {
-          gf_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
           const uint8_t* arow = smem + ((16 * rg + i16) * SA + 8 * g) * 2;
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            const gf_f16x8 ah = *reinterpret_cast<const gf_f16x8*>(arow + 64 * ks);
-            const gf_f16x8 al = *reinterpret_cast<const gf_f16x8*>(arow + 64 * ks + a_plane);
-            const gf_f16x8 bh = __builtin_bit_cast(gf_f16x8, bfr[n][ks][0]), bl = __builtin_bit_cast(gf_f16x8, bfr[n][ks][1]);
+            const f16x8 ah = *reinterpret_cast<const f16x8*>(arow + 64 * ks);
+            const f16x8 al = *reinterpret_cast<const f16x8*>(arow + 64 * ks + a_plane);
+            const f16x8 bh = __builtin_bit_cast(f16x8, bfr[n][ks][0]), bl = __builtin_bit_cast(f16x8, bfr[n][ks][1]);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
             acc_hl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc_hl, 0, 0, 0);
             acc_lh = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc_lh, 0, 0, 0);
@@ -677,7 +638,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
             const int row = 16 * rg + 4 * g + r;
             if (row < p.max_rows) {
               _Float16 h, l;
-              gf_split(acc[r] + (acc_hl[r] + acc_lh[r]) * (1.0f / kGfLoScale), h, l);
+              split(combine(acc[r], acc_hl[r] + acc_lh[r]), h, l);
 #pragma unroll
               for (int d = 0; d < 2; ++d) {
                 const int k = d ? (int)(col_dest[n] >> 16) : (int)(col_dest[n] & 0xFFFFu);
@@ -733,13 +694,13 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
             if (k0 + e < p.L) v[e] = src[k0 + e];
         }
       }
-      gf_f16x8 hi, lo;
+      f16x8 hi, lo;
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = ldexpf(v[e], -h_exp);
-      gf_split8(v, hi, lo);
+      split8(v, hi, lo);
       unsigned char* dst = s_taps + row * p.tap_row_bytes + (half * (p.Q + 1) + q) * 16;
-      *reinterpret_cast<gf_f16x8*>(dst) = hi;
-      *reinterpret_cast<gf_f16x8*>(dst + p.tap_plane) = lo;
+      *reinterpret_cast<f16x8*>(dst) = hi;
+      *reinterpret_cast<f16x8*>(dst + p.tap_plane) = lo;
     }
   }
 
@@ -755,7 +716,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
     const int el = 16 + kGfSlot * sl + 79 - ((s & 15) + within);
     _Float16 hi, lo;
     if constexpr (!GEN) val = ldexpf(val, -x_exp);
-    gf_split(val, hi, lo);
+    split(val, hi, lo);
     *reinterpret_cast<_Float16*>(s_x + 2 * el) = hi;
     *reinterpret_cast<_Float16*>(s_x + p.x_o + 2 * (el + 1)) = hi;
     if constexpr (!GEN) {
@@ -792,11 +753,11 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
 
   // ---- a wavefront's run of pieces -------------------------------------------------------------------------------------
   const int i16 = lane & 15, g = lane >> 4;
-  gf_f32x4 acc[NT], acc_x[NT];
+  f32x4 acc[NT], acc_x[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    acc[t] = (gf_f32x4){0.f, 0.f, 0.f, 0.f};
-    acc_x[t] = (gf_f32x4){0.f, 0.f, 0.f, 0.f};
+    acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    acc_x[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   unsigned touched = 0;
   int Z_run = 0;
@@ -816,14 +777,14 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
       if (!have) { Z_run = s & ~15; have = true; }
       const int colbase = ((s & ~15) - Z_run) >> 4;
       const uint8_t* xa = s_x + x_lane + 2 * kGfSlot * (v - Vt0);
-      gf_f16x8 ah[3], al[3];
+      f16x8 ah[3], al[3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const GfU4 qh = *reinterpret_cast<const GfU4*>(xa - 64 * c);          // 32 elements down per step
-        ah[c] = __builtin_bit_cast(gf_f16x8, qh);
+        const PackedU4 qh = *reinterpret_cast<const PackedU4*>(xa - 64 * c);          // 32 elements down per step
+        ah[c] = __builtin_bit_cast(f16x8, qh);
         if constexpr (!GEN) {
-          const GfU4 ql = *reinterpret_cast<const GfU4*>(xa - 64 * c + x_lo);
-          al[c] = __builtin_bit_cast(gf_f16x8, ql);
+          const PackedU4 ql = *reinterpret_cast<const PackedU4*>(xa - 64 * c + x_lo);
+          al[c] = __builtin_bit_cast(f16x8, ql);
         }
       }
       const uint8_t* trow = s_taps + (f - f_lo) * p.tap_row_bytes;
@@ -837,8 +798,8 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
         for (int c = 0; c < 3; ++c) {
           const int q = 16 * t + q_lane - 2 * c;
           const int grp = (q >= 0 && q < p.Q) ? half_off + q : p.Q;
-          const gf_f16x8 bh = *reinterpret_cast<const gf_f16x8*>(trow + 16 * grp);
-          const gf_f16x8 bl = *reinterpret_cast<const gf_f16x8*>(trow + 16 * grp + p.tap_plane);
+          const f16x8 bh = *reinterpret_cast<const f16x8*>(trow + 16 * grp);
+          const f16x8 bl = *reinterpret_cast<const f16x8*>(trow + 16 * grp + p.tap_plane);
           acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[c], bh, acc[t], 0, 0, 0);
           acc_x[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[c], bl, acc_x[t], 0, 0, 0);
           if constexpr (!GEN) acc_x[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[c], bh, acc_x[t], 0, 0, 0);
@@ -852,7 +813,7 @@ __global__ __launch_bounds__(512, (NT == 4 && NPW == 1) ? 6 : 1) void tv_fir_mfm
   // the kernel's 48 us at 100 bands and batch 32: an LDS float atomic costs ~100 clocks of the CU's one LDS pipeline.)
   // D[row 4 g + r][column a]: outputs 16 a + 4 g + r - a lane's four values are 16 aligned bytes
   float* const o_run = s_out + (Z_run - Z_t0) + 16 * i16 + 4 * g;
-  auto fin = [&](float a, float ax) { return ldexpf(a + ax * (1.0f / kGfLoScale), o_exp); };    // (the exponents of audio and taps back)
+  auto fin = [&](float a, float ax) { return ldexpf(combine(a, ax), o_exp); };    // (the exponents of audio and taps back)
   int head = 0, limit = 0;
   if (have) {
     int fd;
@@ -1005,7 +966,7 @@ static int gf_launch(GfPlan& pl, int B, int Bir, int F, int L, int N, int start,
   DDSP_GF_CASE(4, 1, 2) DDSP_GF_CASE(4, 2, 2) DDSP_GF_CASE(4, 3, 2) DDSP_GF_CASE(4, 4, 2)
   return DDSP_ERR_UNSUPPORTED;
 #undef DDSP_GF_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 int launch_tv_fir_mfma(const float* x, const float* ir, float* out, int B, int Bir, int F, int L, int N, int start,
@@ -1091,13 +1052,12 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
   const int P = p.NF * p.npf;                                   // pieces of 64 samples
 
   // the constant fragments of this wavefront's first task of the second product, requested now
-  typedef uint32_t gi_u32x4 __attribute__((ext_vector_type(4)));
   const int RG = p.NF >> 4;                                     // row groups of 16 frames
   const int n_tasks = RG * 5;                                   // (row group, band tile): 65 bands = 5 tiles
-  gi_u32x4 cfr[4][2];                                           // (one task's at a time: 32 registers, three blocks per CU)
+  u32x4 cfr[4][2];                                           // (one task's at a time: 32 registers, three blocks per CU)
   auto fetch_task = [&](int task) {
     const int nb = task / RG;
-    const gi_u32x4* src = reinterpret_cast<const gi_u32x4*>(p.ct) + (size_t)nb * 4 * 128 + lane;
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.ct) + (size_t)nb * 4 * 128 + lane;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       cfr[ks][0] = src[(2 * ks + 0) * 64];
@@ -1160,10 +1120,10 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = ldexpf(gv[u][e], -g_exp);
-      gf_f16x8 hi, lo;
-      gf_split8(v, hi, lo);
-      *reinterpret_cast<gf_f16x8*>(s_gz + 16 * k) = hi;
-      *reinterpret_cast<gf_f16x8*>(s_gz + p.gz_plane + 16 * k) = lo;
+      f16x8 hi, lo;
+      split8(v, hi, lo);
+      *reinterpret_cast<f16x8*>(s_gz + 16 * k) = hi;
+      *reinterpret_cast<f16x8*>(s_gz + p.gz_plane + 16 * k) = lo;
     }
   }
   {
@@ -1173,7 +1133,7 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
       const int el = 31 + kGfSlot * (rel >> 6) + (rel & 63);
       _Float16 hi, lo;
       if constexpr (!GEN) val = ldexpf(val, -x_exp);
-      gf_split(val, hi, lo);
+      split(val, hi, lo);
       *reinterpret_cast<_Float16*>(s_x + 2 * el) = hi;
       *reinterpret_cast<_Float16*>(s_x + p.x_o + 2 * (el + 1)) = hi;
       if constexpr (!GEN) {
@@ -1214,7 +1174,7 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
     const int half_col = i16 >> 3;                               // which frame of the pair this lane's column belongs to
 #pragma unroll 1
     for (int pp = wave; pp < p.NF / 2; pp += 8) {
-      gf_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_x = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_x = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
       for (int c = 0; c < p.npf; ++c) {
 #pragma unroll
@@ -1225,17 +1185,17 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
           const int base = fr * p.fs + 64 * c;                   // the piece's first sample relative to the tile: a multiple of 8
 #pragma unroll
           for (int ks = 0; ks < 3; ++ks) {
-            const GfU4 qh = *reinterpret_cast<const GfU4*>(xa - 64 * ks);
-            const gf_f16x8 ah = __builtin_bit_cast(gf_f16x8, qh);
+            const PackedU4 qh = *reinterpret_cast<const PackedU4*>(xa - 64 * ks);
+            const f16x8 ah = __builtin_bit_cast(f16x8, qh);
             const int q = (i16 & 7) + 4 - 2 * ks - (g >> 1);     // block of 16 gradient samples this lane's column reads
             const int off = (half_col == half && q >= 0) ? 2 * (base + 16 * q + 8 * (g & 1)) : zero_at;
-            const gf_f16x8 bh = *reinterpret_cast<const gf_f16x8*>(s_gz + off);
-            const gf_f16x8 bl = *reinterpret_cast<const gf_f16x8*>(s_gz + p.gz_plane + off);
+            const f16x8 bh = *reinterpret_cast<const f16x8*>(s_gz + off);
+            const f16x8 bl = *reinterpret_cast<const f16x8*>(s_gz + p.gz_plane + off);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
             acc_x = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc_x, 0, 0, 0);
             if constexpr (!GEN) {
-              const GfU4 ql = *reinterpret_cast<const GfU4*>(xa - 64 * ks + p.x_part);
-              acc_x = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gf_f16x8, ql), bh, acc_x, 0, 0, 0);
+              const PackedU4 ql = *reinterpret_cast<const PackedU4*>(xa - 64 * ks + p.x_part);
+              acc_x = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ql), bh, acc_x, 0, 0, 0);
             }
           }
         }
@@ -1243,10 +1203,10 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
       // D[row 4 g + r][column]: tap 16 (column & 7) + 4 g + r of frame 2 pp + (column >> 3): four consecutive halves
       _Float16 hi[4], lo[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) gf_split(acc[r] + acc_x[r] * (1.0f / kGfLoScale), hi[r], lo[r]);
+      for (int r = 0; r < 4; ++r) split(combine(acc[r], acc_x[r]), hi[r], lo[r]);
       _Float16* dst = s_dh + (2 * pp + half_col) * kNbDhStride + 16 * (i16 & 7) + 4 * g;
-      *reinterpret_cast<uint2*>(dst) = make_uint2(gf_pack(hi[0], hi[1]), gf_pack(hi[2], hi[3]));
-      *reinterpret_cast<uint2*>(dst + p.NF * kNbDhStride) = make_uint2(gf_pack(lo[0], lo[1]), gf_pack(lo[2], lo[3]));
+      *reinterpret_cast<uint2*>(dst) = make_uint2(pack(hi[0], hi[1]), pack(hi[2], hi[3]));
+      *reinterpret_cast<uint2*>(dst + p.NF * kNbDhStride) = make_uint2(pack(lo[0], lo[1]), pack(lo[2], lo[3]));
     }
   }
   __syncthreads();
@@ -1257,13 +1217,13 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
   for (int task = wave; task < n_tasks; task += 8) {             // (wave-uniform)
     if (task != wave) fetch_task(task);                          // (the second task of wavefronts 0, 1: its fragments only now)
     const int nb = task / RG, rg = task - nb * RG;
-    gf_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
     const _Float16* arow = s_dh + (16 * rg + i16) * kNbDhStride + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const gf_f16x8 ah = *reinterpret_cast<const gf_f16x8*>(arow + 32 * ks);
-      const gf_f16x8 al = *reinterpret_cast<const gf_f16x8*>(arow + 32 * ks + p.NF * kNbDhStride);
-      const gf_f16x8 bh = __builtin_bit_cast(gf_f16x8, cfr[ks][0]), bl = __builtin_bit_cast(gf_f16x8, cfr[ks][1]);
+      const f16x8 ah = *reinterpret_cast<const f16x8*>(arow + 32 * ks);
+      const f16x8 al = *reinterpret_cast<const f16x8*>(arow + 32 * ks + p.NF * kNbDhStride);
+      const f16x8 bh = __builtin_bit_cast(f16x8, cfr[ks][0]), bl = __builtin_bit_cast(f16x8, cfr[ks][1]);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
       acc_hl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc_hl, 0, 0, 0);
       acc_lh = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc_lh, 0, 0, 0);
@@ -1275,7 +1235,7 @@ __global__ __launch_bounds__(512, 6) void noise_bwd_mfma_kernel(NbArgs p) {
         const int f = f0 + 16 * rg + 4 * g + r;
         if (f < p.F) {
           const size_t at = ((size_t)b * p.F + f) * p.M + band;
-          float v = ldexpf(acc[r] + (acc_hl[r] + acc_lh[r]) * (1.0f / kGfLoScale), g_exp + x_exp);
+          float v = ldexpf(combine(acc[r], acc_hl[r] + acc_lh[r]), g_exp + x_exp);
           if (p.scale) {
             const float xr = p.mag[at] + p.bias;
             const float y = exp_sigmoid_fast(xr, kLog10, 2.0f, 1e-7f);
@@ -1330,7 +1290,7 @@ int launch_noise_bwd_mfma(const float* magnitudes, const float* noise, const flo
   ProfileScope prof(kNoiseBwdMfma, st);
   if (lo_planes) hipLaunchKernelGGL((noise_bwd_mfma_kernel<false>), grid, dim3(512), lds, st, a);
   else hipLaunchKernelGGL((noise_bwd_mfma_kernel<true>), grid, dim3(512), lds, st, a);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 }  // namespace ddsp

@@ -41,9 +41,11 @@
 #include <type_traits>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "split_f16.h"
 #include "noise_ir65.h"
 #include "profile.h"
 #include "filtered_noise_mfma.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -61,7 +63,6 @@ constexpr int kMfRows = 8 * kMfPW;             // staged frames: 2 of history + 
                                                // x 2 tap tiles; an FIR wavefront = 4 pairs = 8 frames): 32
 constexpr int kMfFrames = kMfRows - 2;         // output frames per tile: 30
 constexpr int kMfTile = kMfFrames * 64;        // 1920 output samples per tile
-constexpr float kMfLoScale = 2048.0f;          // x = hi + lo / 2048 in two fp16 numbers
 // tap table: a hi plane and a lo plane; per row 16 groups of 8 taps (16 bytes) + one group of zeros that lanes outside the
 // filter's support read.  The 16 lanes of a ds_read_b128 pass read 16 DIFFERENT groups of one row (or the zero group):
 // with 16-byte groups they cover all 64 banks once (32-byte {hi, lo} groups were a 2-way conflict, and the LDS is what
@@ -95,10 +96,6 @@ struct MfHandoff {
   float tap32[kMfRows];                // window[32] * sum over even bins of cos(pi m / 2) m (taps 32 and 96)
 };
 
-typedef _Float16 mf_f16x8 __attribute__((ext_vector_type(8)));
-typedef float mf_f32x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 mf_h16x2 __attribute__((ext_vector_type(2)));
-
 struct MfArgs {
   int N, F, start, scale, fs;       // fs = frame size (64: one tap row per staged frame; 64 c: c staged frames per row)
   float inv_fs;
@@ -116,52 +113,27 @@ struct MfArgs {
   int bits23;
 };
 
-struct __attribute__((packed, aligned(4))) MfU4f { float x, y, z, w; };        // 16 bytes from a 4-byte aligned address
-struct __attribute__((packed, aligned(4))) MfU4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ uint32_t mf_pack(_Float16 a, _Float16 b) {
-  return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-}
-__device__ __forceinline__ void mf_split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)((v - (float)hi) * kMfLoScale);
-}
-__device__ __forceinline__ void mf_split8(const float (&v)[8], mf_f16x8& hi, mf_f16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    _Float16 h, l;
-    mf_split(v[e], h, l);
-    hi[e] = h;
-    lo[e] = l;
-  }
-}
-__device__ __forceinline__ mf_f16x8 mf_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {a, b, c, d};
-  return __builtin_bit_cast(mf_f16x8, v);
-}
-
 static __constant__ Ir65Frags kIr65Frags = make_ir65_frags();
 
 // Four taps that sit next to each other in a row of the tap table, v[0] at tap t0 (t0 a multiple of 4): split and
 // stored as two 8-byte pieces (hi part, lo part).
 __device__ __forceinline__ void mf_put4(unsigned char* hrow, int t0, float v0, float v1, float v2, float v3) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  mf_split(v0, h0, l0); mf_split(v1, h1, l1); mf_split(v2, h2, l2); mf_split(v3, h3, l3);
+  split(v0, h0, l0); split(v1, h1, l1); split(v2, h2, l2); split(v3, h3, l3);
   unsigned char* q = hrow + t0 * 2;
-  *reinterpret_cast<uint2*>(q) = make_uint2(mf_pack(h0, h1), mf_pack(h2, h3));
-  *reinterpret_cast<uint2*>(q + kMfTapPlane) = make_uint2(mf_pack(l0, l1), mf_pack(l2, l3));
+  *reinterpret_cast<uint2*>(q) = make_uint2(pack(h0, h1), pack(h2, h3));
+  *reinterpret_cast<uint2*>(q + kMfTapPlane) = make_uint2(pack(l0, l1), pack(l2, l3));
 }
 // The mirror image: v[0] at tap t1, v[1] at t1 - 1, ... v[3] at t1 - 3 (t1 a multiple of 4; t1 itself is skipped when
 // `first` is false).  t1 - 1, t1 - 2 share a dword; t1 - 3 and t1 are single halves.
 __device__ __forceinline__ void mf_put4_down(unsigned char* hrow, int t1, bool first, float v0, float v1, float v2, float v3) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  mf_split(v0, h0, l0); mf_split(v1, h1, l1); mf_split(v2, h2, l2); mf_split(v3, h3, l3);
+  split(v0, h0, l0); split(v1, h1, l1); split(v2, h2, l2); split(v3, h3, l3);
   unsigned char* q = hrow + (t1 - 3) * 2;                            // taps t1-3 (odd element), then the dword (t1-2, t1-1)
   *reinterpret_cast<uint16_t*>(q) = __builtin_bit_cast(uint16_t, h3);
   *reinterpret_cast<uint16_t*>(q + kMfTapPlane) = __builtin_bit_cast(uint16_t, l3);
-  *reinterpret_cast<uint32_t*>(q + 2) = mf_pack(h2, h1);
-  *reinterpret_cast<uint32_t*>(q + kMfTapPlane + 2) = mf_pack(l2, l1);
+  *reinterpret_cast<uint32_t*>(q + 2) = pack(h2, h1);
+  *reinterpret_cast<uint32_t*>(q + kMfTapPlane + 2) = pack(l2, l1);
   if (first) {
     *reinterpret_cast<uint16_t*>(q + 6) = __builtin_bit_cast(uint16_t, h0);
     *reinterpret_cast<uint16_t*>(q + kMfTapPlane + 6) = __builtin_bit_cast(uint16_t, l0);
@@ -173,24 +145,24 @@ __device__ __forceinline__ void mf_put4_down(unsigned char* hrow, int t1, bool f
 template <bool LO>
 __device__ __forceinline__ void mf_put_quad(float4 v, int qd, unsigned char* s_xe, unsigned char* s_xo) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  mf_split(v.w, h0, l0);               // element u0     = sample j + 3
-  mf_split(v.z, h1, l1);               // element u0 + 1 = sample j + 2
-  mf_split(v.y, h2, l2);
-  mf_split(v.x, h3, l3);
+  split(v.w, h0, l0);               // element u0     = sample j + 3
+  split(v.z, h1, l1);               // element u0 + 1 = sample j + 2
+  split(v.y, h2, l2);
+  split(v.x, h3, l3);
   const int s = qd >> 4, j = 4 * (qd & 15);
   const int u0 = 16 + kMfXStride * s + 60 - j;                     // a multiple of 4
   // copy E: dwords u0/2 and u0/2 + 1 of each plane (8 bytes, 8-byte aligned)
-  *reinterpret_cast<uint2*>(s_xe + u0 * 2) = make_uint2(mf_pack(h0, h1), mf_pack(h2, h3));
-  if (LO) *reinterpret_cast<uint2*>(s_xe + kMfXPlane + u0 * 2) = make_uint2(mf_pack(l0, l1), mf_pack(l2, l3));
+  *reinterpret_cast<uint2*>(s_xe + u0 * 2) = make_uint2(pack(h0, h1), pack(h2, h3));
+  if (LO) *reinterpret_cast<uint2*>(s_xe + kMfXPlane + u0 * 2) = make_uint2(pack(l0, l1), pack(l2, l3));
   // copy O: element e is half (e + 1) & 1 of dword (e + 1) >> 1, i.e. at byte 2 (e + 1): u0 -> high half of
   // dword u0/2, (u0+1, u0+2) -> dword u0/2 + 1, u0+3 -> low half of dword u0/2 + 2
   unsigned char* po = s_xo + (u0 + 1) * 2;
   *reinterpret_cast<uint16_t*>(po) = __builtin_bit_cast(uint16_t, h0);
-  *reinterpret_cast<uint32_t*>(po + 2) = mf_pack(h1, h2);
+  *reinterpret_cast<uint32_t*>(po + 2) = pack(h1, h2);
   *reinterpret_cast<uint16_t*>(po + 6) = __builtin_bit_cast(uint16_t, h3);
   if (LO) {
     *reinterpret_cast<uint16_t*>(po + kMfXPlane) = __builtin_bit_cast(uint16_t, l0);
-    *reinterpret_cast<uint32_t*>(po + kMfXPlane + 2) = mf_pack(l1, l2);
+    *reinterpret_cast<uint32_t*>(po + kMfXPlane + 2) = pack(l1, l2);
     *reinterpret_cast<uint16_t*>(po + kMfXPlane + 6) = __builtin_bit_cast(uint16_t, l3);
   }
 }
@@ -348,7 +320,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     };
     // the 16 bins of this lane's B-fragments (row = 16 rg + i, bins 16 g .. + 15) and bin 64 of that row, straight from
     // HBM; rows outside [0, F) are fetched from frame 0 and masked afterwards (unconditional loads)
-    MfU4f rq[4];
+    PackedF4 rq[4];
     float r_last;
     auto fetch_rows = [&](int tick_of_tile) {        // the rows of the block's tile number `tick_of_tile` (clamped to its last)
       const int T = (int)blockIdx.x + min(max(tick_of_tile, 0), n_my - 1) * (int)gridDim.x;
@@ -357,12 +329,12 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       const int rfr = f_first + rrow;
       const float* __restrict__ src = mag + ((size_t)b * p.F + ((rfr >= 0 && rfr < p.F) ? rfr : 0)) * 65;
 #pragma unroll
-      for (int c4 = 0; c4 < 4; ++c4) rq[c4] = *reinterpret_cast<const MfU4f*>(src + 16 * mg + 4 * c4);
+      for (int c4 = 0; c4 < 4; ++c4) rq[c4] = *reinterpret_cast<const PackedF4*>(src + 16 * mg + 4 * c4);
       r_last = src[64];
     };
     // the fetched rows of tile T scaled, masked and split: the four B-fragments, bin 64, tap 32's value; the controls written.
     // (false: the tile's rows lie past the end of the clip - nobody reads their taps)
-    auto scale_rows = [&](int T, mf_f16x8& be_hi, mf_f16x8& be_lo, mf_f16x8& bo_hi, mf_f16x8& bo_lo, float& m_last, float& t32) -> bool {
+    auto scale_rows = [&](int T, f16x8& be_hi, f16x8& be_lo, f16x8& bo_hi, f16x8& bo_lo, float& m_last, float& t32) -> bool {
       DDSP_MF_TILE(T, b, z0, f_first, rel0);
       // controls ownership: tile t writes frames [own_lo, own_hi) so that every frame is written once
       const int own_lo = (z0 == 0) ? 0 : f_first + 2;
@@ -390,14 +362,14 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
         float* __restrict__ dst = ctl_out + ((size_t)b * p.F + rfr) * 65;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4)
-          *reinterpret_cast<MfU4f*>(dst + 16 * mg + 4 * c4) = MfU4f{y[4 * c4], y[4 * c4 + 1], y[4 * c4 + 2], y[4 * c4 + 3]};
+          *reinterpret_cast<PackedF4*>(dst + 16 * mg + 4 * c4) = PackedF4{y[4 * c4], y[4 * c4 + 1], y[4 * c4 + 2], y[4 * c4 + 3]};
         if (mg == 0) dst[64] = m_last;
       }
       float ve[8], vo[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { ve[e] = y[2 * e]; vo[e] = y[2 * e + 1]; }
-      mf_split8(ve, be_hi, be_lo);
-      mf_split8(vo, bo_hi, bo_lo);
+      split8(ve, be_hi, be_lo);
+      split8(vo, bo_hi, bo_lo);
       // tap 32: cos(pi m / 2) vanishes for odd bins; this lane's 8 even bins, then the row's four lanes together
       const float* __restrict__ c32 = kIr65.c + 32 * kIrRowStride + 8 * mg;
       float part = (mg == 0) ? m_last * kIr65.c[32 * kIrRowStride + 32] : 0.0f;
@@ -431,7 +403,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           if (tick + 2 < n_my) {
             const int T = (int)blockIdx.x + (tick + 2) * (int)gridDim.x;
             MfHandoff& h = s_hand[(tick + 2) & 1];
-            mf_f16x8 be_hi, be_lo, bo_hi, bo_lo;
+            f16x8 be_hi, be_lo, bo_hi, bo_lo;
             float m_last, t32;
             if (scale_rows(T, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) {
               h.frag[rg][0][lane] = __builtin_bit_cast(uint4, be_hi);
@@ -450,7 +422,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       // ------------------------- designers ----------------------------------------------------------------------------
       // the constant cosine factor of both tap tiles as fp16 hi / lo A-fragments, made at compile time:
       // [tap tile][even / odd bins][hi / lo]
-      mf_f16x8 afr[2][2][2];
+      f16x8 afr[2][2][2];
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -458,23 +430,23 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
 #pragma unroll
           for (int hl = 0; hl < 2; ++hl) {
             const uint4 v = *reinterpret_cast<const uint4*>(kIr65Frags.v[mt][par][hl][lane]);
-            afr[mt][par][hl] = mf_frag(v.x, v.y, v.z, v.w);
+            afr[mt][par][hl] = frag(v.x, v.y, v.z, v.w);
           }
       // the two tap tiles of this wavefront's rows from their scaled, split magnitudes
-      auto design_rows = [&](unsigned char* s_taps, const mf_f16x8& be_hi, const mf_f16x8& be_lo, const mf_f16x8& bo_hi,
-                             const mf_f16x8& bo_lo, float m_last, float t32) {
+      auto design_rows = [&](unsigned char* s_taps, const f16x8& be_hi, const f16x8& be_lo, const f16x8& bo_hi,
+                             const f16x8& bo_lo, float m_last, float t32) {
           unsigned char* __restrict__ hrow = s_taps + rrow * kMfTapRowBytes;
-          const mf_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+          const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt) {
             // e(n) = sum_i ce[n][i] m[2i], o(n) = sum_i co[n][i] m[2i+1], n = 16 mt + 4 g + r: D[n][row i]
-            mf_f32x4 ea = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][0][0], be_hi, zero, 0, 0, 0);
-            mf_f32x4 oa = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][1][0], bo_hi, zero, 0, 0, 0);
-            mf_f32x4 ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][0][0], be_lo, zero, 0, 0, 0);
-            mf_f32x4 ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][1][0], bo_lo, zero, 0, 0, 0);
+            f32x4 ea = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][0][0], be_hi, zero, 0, 0, 0);
+            f32x4 oa = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][1][0], bo_hi, zero, 0, 0, 0);
+            f32x4 ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][0][0], be_lo, zero, 0, 0, 0);
+            f32x4 ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][1][0], bo_lo, zero, 0, 0, 0);
             ex = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][0][1], be_hi, ex, 0, 0, 0);
             ox = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[mt][1][1], bo_hi, ox, 0, 0, 0);
-            const mf_f32x4 ev = ea + ex * (1.0f / kMfLoScale), ov = oa + ox * (1.0f / kMfLoScale);
+            const f32x4 ev = combine(ea, ex), ov = combine(oa, ox);
             const int n0 = 16 * mt + 4 * mg;                                // this lane's taps n0 .. n0 + 3
             float g0[4], g1[4];
 #pragma unroll
@@ -492,7 +464,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           }
           if (mg == 0) {                                                     // tap 32 (and its mirror image, tap 96)
             _Float16 h, l;
-            mf_split(t32, h, l);
+            split(t32, h, l);
             const uint16_t hb = __builtin_bit_cast(uint16_t, h), lb = __builtin_bit_cast(uint16_t, l);
             *reinterpret_cast<uint16_t*>(hrow + 96 * 2) = hb;              // tap 96
             *reinterpret_cast<uint16_t*>(hrow + kMfTapPlane + 96 * 2) = lb;
@@ -509,7 +481,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           const int T = (int)blockIdx.x + (tick + 1) * (int)gridDim.x;
           unsigned char* const s_taps = s_taps_all[(tick + 1) & 1];
           if constexpr (SCALE_HERE) {
-            mf_f16x8 be_hi, be_lo, bo_hi, bo_lo;
+            f16x8 be_hi, be_lo, bo_hi, bo_lo;
             float m_last = 0.0f, t32 = 0.0f;
             if (scale_rows(T, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) design_rows(s_taps, be_hi, be_lo, bo_hi, bo_lo, m_last, t32);
           } else if constexpr (HANDOFF) {
@@ -517,8 +489,8 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
             (void)b;
             if (f_first + 16 * rg <= p.F + 1 && !group_unused(rel0, z0, f_first)) {        // (the noise maker's own test: scale_rows)
               const MfHandoff& h = s_hand[(tick + 1) & 1];
-              design_rows(s_taps, __builtin_bit_cast(mf_f16x8, h.frag[rg][0][lane]), __builtin_bit_cast(mf_f16x8, h.frag[rg][1][lane]),
-                          __builtin_bit_cast(mf_f16x8, h.frag[rg][2][lane]), __builtin_bit_cast(mf_f16x8, h.frag[rg][3][lane]),
+              design_rows(s_taps, __builtin_bit_cast(f16x8, h.frag[rg][0][lane]), __builtin_bit_cast(f16x8, h.frag[rg][1][lane]),
+                          __builtin_bit_cast(f16x8, h.frag[rg][2][lane]), __builtin_bit_cast(f16x8, h.frag[rg][3][lane]),
                           h.last[rrow], h.tap32[rrow]);
             }
           }
@@ -551,7 +523,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // what bounds this phase).
     const int cw = wave - kMfPW;
     const int p_first = 4 * cw;
-    mf_f32x4 kept = {0.f, 0.f, 0.f, 0.f};      // the incomplete left half of this wavefront's first pair (cw >= 1), last tile
+    f32x4 kept = {0.f, 0.f, 0.f, 0.f};      // the incomplete left half of this wavefront's first pair (cw >= 1), last tile
     float* kept_ot = nullptr;                  // where it goes: the tile's base pointer, offset and bounds of the previous tick
     long kept_n = 0;
     int kept_exp = 0;                          // (supplied noise: the exponent its row was normalised by)
@@ -615,7 +587,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
         if constexpr (!GEN_NOISE) {
           if (p.x_absmax) o_exp = pow2_exponent(p.x_absmax[b]);
         }
-        mf_f32x4 carry = {0.f, 0.f, 0.f, 0.f};
+        f32x4 carry = {0.f, 0.f, 0.f, 0.f};
         int a_hi[2], a_lo[2], b_ptr = b_ptr0;
         DDSP_KEEP_IN_VGPR(b_ptr);
         __builtin_assume((b_ptr & 15) == 0);
@@ -635,14 +607,14 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
         // with many operations outstanding, and two FIR wavefronts share a SIMD), the epilogue of a pair (combine, store,
         // shift the right half over) runs under the reads of the next pair.  The carry enters in the epilogue, not as
         // the accumulator's start value, so no MFMA waits for a previous pair.
-        mf_f16x8 fah[3], fal[3], fbh_in[2], fbl_in[2], fbh, fbl;
+        f16x8 fah[3], fal[3], fbh_in[2], fbl_in[2], fbh, fbl;
         auto load_step = [&](int j, int slot) {
           const int it = j / 5, c = j - 5 * it;
-          const MfU4 qh = *reinterpret_cast<const MfU4*>(s_x + a_hi[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
-          fah[slot] = mf_frag(qh.x, qh.y, qh.z, qh.w);
+          const PackedU4 qh = *reinterpret_cast<const PackedU4*>(s_x + a_hi[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
+          fah[slot] = frag(qh.x, qh.y, qh.z, qh.w);
           if constexpr (!GEN_NOISE) {           // (generated noise is fp16 as it stands: no lo plane, no lo . hi product)
-            const MfU4 ql = *reinterpret_cast<const MfU4*>(s_x + a_lo[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
-            fal[slot] = mf_frag(ql.x, ql.y, ql.z, ql.w);
+            const PackedU4 ql = *reinterpret_cast<const PackedU4*>(s_x + a_lo[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
+            fal[slot] = frag(ql.x, ql.y, ql.z, ql.w);
           }
           if (c == 0) {
             // the pair's taps: first frame's row in lanes g < 2, second frame's in g >= 2
@@ -655,12 +627,12 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
               const int row = (int)(((float)(rel0 + 128 * P + 64 * second) + 0.5f) * p.inv_fs);
               tr = s_taps + row * kMfTapRowBytes + b_off;
             }
-            fbh_in[it & 1] = *reinterpret_cast<const mf_f16x8*>(tr);
-            fbl_in[it & 1] = *reinterpret_cast<const mf_f16x8*>(tr + kMfTapPlane);
+            fbh_in[it & 1] = *reinterpret_cast<const f16x8*>(tr);
+            fbl_in[it & 1] = *reinterpret_cast<const f16x8*>(tr + kMfTapPlane);
           }
         };
         // one column up (row_shr:1 within the 16 lanes of a g; column 0 receives zeros)
-        auto column_up = [](mf_f16x8 v) {
+        auto column_up = [](f16x8 v) {
           typedef int i32x4 __attribute__((ext_vector_type(4)));
           const i32x4 w = __builtin_bit_cast(i32x4, v);
           i32x4 o;
@@ -669,13 +641,13 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
             const int t = w[k];                // (a scalar temporary: see the carry below)
             o[k] = __builtin_amdgcn_update_dpp(0, t, 0x111, 0xF, 0xF, true);
           }
-          return __builtin_bit_cast(mf_f16x8, o);
+          return __builtin_bit_cast(f16x8, o);
         };
         load_step(0, 0);
         load_step(1, 1);
         load_step(2, 2);
         __builtin_amdgcn_sched_barrier(0);
-        mf_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};   // three independent chains
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};   // three independent chains
         auto pipeline = [&](auto interior_tag) {
           constexpr bool kInterior = decltype(interior_tag)::value;
 #pragma unroll
@@ -690,16 +662,16 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
             if (c < 4) { fbh = column_up(fbh); fbl = column_up(fbl); }      // under the MFMAs
             __builtin_amdgcn_sched_barrier(0);
             if (c == 4) {
-              const mf_f32x4 comb = (acc + carry) + (acc_hl + acc_lh) * (1.0f / kMfLoScale);
-              acc = (mf_f32x4){0.f, 0.f, 0.f, 0.f};
-              acc_hl = (mf_f32x4){0.f, 0.f, 0.f, 0.f};
-              acc_lh = (mf_f32x4){0.f, 0.f, 0.f, 0.f};
+              const f32x4 comb = combine(acc + carry, acc_hl + acc_lh);
+              acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+              acc_hl = (f32x4){0.f, 0.f, 0.f, 0.f};
+              acc_lh = (f32x4){0.f, 0.f, 0.f, 0.f};
               // D[row b = 4 g + r][col a = i]: columns 0..7 are complete (the first pair's: see above)
               if (it == 0) {
                 kept = comb;
               } else if (mi < 8) {
                 const int idx = lane_off + 128 * it;                         // out index n = n_tile + idx
-                mf_f32x4 st4 = comb;
+                f32x4 st4 = comb;
                 if constexpr (!GEN_NOISE) {
 #pragma unroll
                   for (int r = 0; r < 4; ++r) { const float v = comb[r]; st4[r] = ldexpf(v, o_exp); }
@@ -804,7 +776,7 @@ int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audi
   if (q.fs == 64) { if (lo_planes) DDSP_LAUNCH_MF(false, true); else DDSP_LAUNCH_MF(true, true); }
   else { if (lo_planes) DDSP_LAUNCH_MF(false, false); else DDSP_LAUNCH_MF(true, false); }
 #undef DDSP_LAUNCH_MF
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 }  // namespace ddsp

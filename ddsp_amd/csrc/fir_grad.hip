@@ -26,12 +26,14 @@
 //                           backward pass, are per-thread strided partials in fp64 added by thread 0 in thread order.
 //   fir_design_backward_kernel   grad_magnitudes[r][m] = sum_k D[k][m] grad_ir[r][k]: the design is linear in the magnitudes,
 //                           D [L, M] is what the forward design kernel makes of the identity (the host layer keeps it).
-//   exp_sigmoid_backward_kernel  elementwise.
+//   exp_sigmoid_kernel / exp_sigmoid_backward_kernel  elementwise.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "launch.h"
+#include "profile.h"
 
 namespace ddsp {
 namespace fir_grad {
@@ -224,6 +226,14 @@ __global__ __launch_bounds__(kThreads) void fir_design_backward_kernel(const flo
   }
 }
 
+__global__ __launch_bounds__(256) void exp_sigmoid_kernel(const float* __restrict__ in,
+                                                          float* __restrict__ out, size_t n,
+                                                          float log_exponent, float max_value,
+                                                          float threshold) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    out[i] = exp_sigmoid(in[i], log_exponent, max_value, threshold);
+}
+
 // ---- d exp_sigmoid / dx = log(exponent) (y - threshold) (1 - sigmoid(x)),  y - threshold = max_value sigmoid(x)^log(exponent) ----
 __global__ __launch_bounds__(kThreads) void exp_sigmoid_backward_kernel(const float* __restrict__ in, const float* __restrict__ grad_out,
                                                                         float* __restrict__ grad_in, size_t n, float log_exponent,
@@ -248,11 +258,10 @@ static int make_args(Args* p, int B, int Bir, int F, int L, int N, int n_out, in
   return DDSP_OK;
 }
 
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
-
 }  // namespace fir_grad
 }  // namespace ddsp
 
+using namespace ddsp;
 using namespace ddsp::fir_grad;
 
 extern "C" int ddsp_fft_convolve_grad_audio_f32(const float* grad_out, const float* impulse_response, float* grad_audio, int B, int Bir,
@@ -335,6 +344,16 @@ extern "C" int ddsp_frequency_impulse_response_backward_f32(const float* grad_im
   if (L > kMaxDesignTaps) return DDSP_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(fir_design_backward_kernel, dim3((unsigned)rows), dim3(kThreads), 0, (hipStream_t)stream, grad_impulse_response,
                      design, grad_magnitudes, M, L);
+  return check_launch();
+}
+
+extern "C" int ddsp_exp_sigmoid_f32(const float* in, float* out, size_t n, float exponent,
+                                    float max_value, float threshold, void* stream) {
+  if (!in || !out) return DDSP_ERR_NULL_POINTER;
+  if (n == 0) return DDSP_OK;
+  ProfileScope prof(kExpSigmoid, (hipStream_t)stream);
+  hipLaunchKernelGGL(exp_sigmoid_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, in,
+                     out, n, logf(exponent), max_value, threshold);
   return check_launch();
 }
 

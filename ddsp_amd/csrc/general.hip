@@ -13,6 +13,8 @@
 //   ddsp_exp_decay_ir_f32 (+ _backward)   effects.ExpDecayReverb's impulse response and its gradient with
 //                                 respect to gain and decay (ddsp/effects.py:120-199)
 //   ddsp_mix_f32, ddsp_sigmoid_f32        processors.Mix (ddsp/processors.py:180-233)
+//   ddsp_resample_f32             core.resample 'linear' / 'window' with the reference's defaults
+//   ddsp_version                  the library's version string
 //
 // These are generality paths: one thread per output value, HBM / L2 reads only, no LDS, no cross-lane
 // traffic, no inline assembly.  Their cost is irrelevant next to the fused kernels of harmonic*.hip and
@@ -23,6 +25,7 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "noise_ir_geom.h"      // hann_denominator: tf.signal.hann_window's denominator
+#include "launch.h"
 
 namespace ddsp {
 namespace general {
@@ -583,17 +586,64 @@ __global__ __launch_bounds__(kThreads) void mix_backward_kernel(const float* __r
   }
 }
 
-static inline unsigned grid_for(size_t n, unsigned cap = 256 * 32) {
-  size_t g = (n + kThreads - 1) / kThreads;
-  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
+// =====================================================================================
+// Stand-alone frame-rate -> audio-rate resampling (core.resample 'linear' / 'window',
+// ddsp/core.py:573-714) for callers that want the envelopes themselves.  The synth kernels
+// never materialise these [B,N,C] tensors; this is an HBM-write-bound elementwise kernel.
+// =====================================================================================
+// out[b,t,c] = x[b,lo,c]*(1-w) + x[b,hi,c]*w with
+//   'linear' (legacy bilinear, align_corners=False): pos = t*fl32(F/N), lo=floor, hi=min(ceil,F-1),
+//             w = pos-lo, evaluated as top + (bottom-top)*w exactly like TF;
+//   'window' (upsample_with_windows, add_endpoint=True): j=t/hop, r=t%hop, hi=min(j+1,F-1),
+//             w = Hann(2*hop)[r] = 0.5-0.5*cos(pi*r/hop), out = x[j]*(1-w) + x[hi]*w.
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x,
+                                                       float* __restrict__ out, int F, int N, int C,
+                                                       int window, float scale, int hop) {
+  const int b = blockIdx.y;
+  const size_t total = (size_t)N * C;
+  const float* __restrict__ xb = x + (size_t)b * F * C;
+  float* __restrict__ ob = out + (size_t)b * total;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int t = (int)(i / C), c = (int)(i - (size_t)t * C);
+    if (window) {
+      const int j = t / hop, r = t - j * hop;
+      const int hi = min(j + 1, F - 1);
+      const float w = 0.5f - 0.5f * cospif((float)r / (float)hop);
+      ob[i] = xb[(size_t)j * C + c] * (1.0f - w) + xb[(size_t)hi * C + c] * w;
+    } else {
+      // every step individually rounded (no FMA contraction of t*scale - lo: found on the MI355X in round 1)
+      const float pos = rn_mul((float)t, scale);
+      const float lo = floorf(pos);
+      const int lo_i = (int)lo, hi_i = min((int)ceilf(pos), F - 1);
+      const float top = xb[(size_t)lo_i * C + c], bottom = xb[(size_t)hi_i * C + c];
+      ob[i] = rn_add(top, rn_mul(rn_sub(bottom, top), rn_sub(pos, lo)));
+    }
+  }
 }
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
+
+constexpr unsigned kMaxBlocks = 256 * 32;      // grid_for's cap where nothing asks for a smaller one
 static inline size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 
 }  // namespace general
 }  // namespace ddsp
 
+using namespace ddsp;
 using namespace ddsp::general;
+
+extern "C" const char* ddsp_version(void) { return "ddsp_amd 0.1.0 gfx950"; }
+
+extern "C" int ddsp_resample_f32(const float* x, float* out, int B, int F, int N, int C, int window,
+                                 void* stream) {
+  if (!x || !out) return DDSP_ERR_NULL_POINTER;
+  if (B <= 0 || F <= 0 || N <= 0 || C <= 0 || B > 65535) return DDSP_ERR_BAD_SHAPE;
+  if (window && (N % F != 0)) return DDSP_ERR_BAD_SHAPE;
+  const float scale = (float)F / (float)N;            // fp32, as TF computes it
+  const size_t total = (size_t)N * C;
+  const dim3 grid(grid_for(total, 2048), (unsigned)B);
+  hipLaunchKernelGGL(resample_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, out, F, N, C,
+                     window, scale, window ? N / F : 1);
+  return check_launch();
+}
 
 extern "C" int ddsp_resample_ex_f32(const float* x, float* out, int B, int F, int N, int C, int method,
                                     int add_endpoint, void* stream) {
@@ -680,7 +730,7 @@ extern "C" int ddsp_apply_window_to_impulse_response_f32(const float* impulse_re
   p.half = (p.ws + 1) / 2;
   p.first_len = p.half > 2 ? p.half - 2 : 0;
   p.L = ddsp_window_impulse_response_size(L0, window_size);
-  hipLaunchKernelGGL(window_ir_kernel, dim3(grid_for((size_t)rows * p.L)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(window_ir_kernel, dim3(grid_for((size_t)rows * p.L, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
                      impulse_response, out, p);
   return check_launch();
 }
@@ -708,7 +758,7 @@ extern "C" int ddsp_harmonic_envelopes_f32(const float* amplitudes, const float*
   if (!amplitudes || !f0_hz || !harmonic_frequencies || !harmonic_amplitudes) return DDSP_ERR_NULL_POINTER;
   if (B <= 0 || F <= 0 || K <= 0) return DDSP_ERR_BAD_SHAPE;
   const size_t rows = (size_t)B * F;
-  hipLaunchKernelGGL(harmonic_envelopes_kernel, dim3(grid_for(rows * K)), dim3(kThreads), 0,
+  hipLaunchKernelGGL(harmonic_envelopes_kernel, dim3(grid_for(rows * K, kMaxBlocks)), dim3(kThreads), 0,
                      (hipStream_t)stream, amplitudes, harmonic_distribution, f0_hz, harmonic_shifts,
                      harmonic_frequencies, harmonic_amplitudes, rows, K);
   return check_launch();
@@ -719,7 +769,7 @@ extern "C" int ddsp_harmonic_frequencies_backward_f32(const float* grad_harmonic
   if (!grad_harmonic_frequencies || !grad_f0_hz) return DDSP_ERR_NULL_POINTER;
   if (B <= 0 || F <= 0 || K <= 0) return DDSP_ERR_BAD_SHAPE;
   const size_t rows = (size_t)B * F;
-  hipLaunchKernelGGL(harmonic_frequencies_backward_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(harmonic_frequencies_backward_kernel, dim3(grid_for(rows, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
                      grad_harmonic_frequencies, harmonic_shifts, grad_f0_hz, rows, K);
   return check_launch();
 }
@@ -727,7 +777,7 @@ extern "C" int ddsp_harmonic_frequencies_backward_f32(const float* grad_harmonic
 extern "C" int ddsp_scale_f32(const float* x, const float* scale, float* out, size_t n, void* stream) {
   if (!x || !scale || !out) return DDSP_ERR_NULL_POINTER;
   if (n == 0) return DDSP_OK;
-  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, x, scale, out, n);
+  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, x, scale, out, n);
   return check_launch();
 }
 
@@ -749,9 +799,9 @@ extern "C" int ddsp_harmonic_oscillator_bank_f32(const float* frequency, const f
   double* sums = (double*)workspace;
   double* total = sums + (size_t)B * C;
   const double inv_sr = 1.0 / (double)sample_rate;
-  hipLaunchKernelGGL(hob_chunk_sums_kernel, dim3(grid_for((size_t)B * C)), dim3(kThreads), 0, st, frequency, sums, B, N, C);
-  hipLaunchKernelGGL(hob_prefix_kernel, dim3(grid_for((size_t)B)), dim3(kThreads), 0, st, sums, total, B, C, inv_sr);
-  hipLaunchKernelGGL(hob_synth_kernel, dim3(grid_for((size_t)B * N)), dim3(kThreads), 0, st, frequency, amplitude_envelopes,
+  hipLaunchKernelGGL(hob_chunk_sums_kernel, dim3(grid_for((size_t)B * C, kMaxBlocks)), dim3(kThreads), 0, st, frequency, sums, B, N, C);
+  hipLaunchKernelGGL(hob_prefix_kernel, dim3(grid_for((size_t)B, kMaxBlocks)), dim3(kThreads), 0, st, sums, total, B, C, inv_sr);
+  hipLaunchKernelGGL(hob_synth_kernel, dim3(grid_for((size_t)B * N, kMaxBlocks)), dim3(kThreads), 0, st, frequency, amplitude_envelopes,
                      initial_phase, sums, total, audio, final_phase, B, N, K, C, inv_sr, use_angular_cumsum ? 1 : 0);
   return check_launch();
 }
@@ -785,12 +835,12 @@ extern "C" int ddsp_harmonic_f0_grad_f32(const float* ctl_amplitudes, const floa
   ws += align_up((size_t)B * F * 3 * sizeof(double), 16);
   float* c = (float*)ws;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(f0grad_phase_kernel, dim3(grid_for((size_t)B)), dim3(kThreads), 0, st, f0_hz, theta0, p);
-  hipLaunchKernelGGL(f0grad_c_kernel, dim3(grid_for((size_t)B * N)), dim3(kThreads), 0, st, ctl_amplitudes,
+  hipLaunchKernelGGL(f0grad_phase_kernel, dim3(grid_for((size_t)B, kMaxBlocks)), dim3(kThreads), 0, st, f0_hz, theta0, p);
+  hipLaunchKernelGGL(f0grad_c_kernel, dim3(grid_for((size_t)B * N, kMaxBlocks)), dim3(kThreads), 0, st, ctl_amplitudes,
                      ctl_harmonic_distribution, f0_hz, (const double*)theta0, grad_audio, c, p);
-  hipLaunchKernelGGL(f0grad_frame_kernel, dim3(grid_for((size_t)B * F)), dim3(kThreads), 0, st,
+  hipLaunchKernelGGL(f0grad_frame_kernel, dim3(grid_for((size_t)B * F, kMaxBlocks)), dim3(kThreads), 0, st,
                      (const float*)c, sums, p);
-  hipLaunchKernelGGL(f0grad_scan_kernel, dim3(grid_for((size_t)B)), dim3(kThreads), 0, st,
+  hipLaunchKernelGGL(f0grad_scan_kernel, dim3(grid_for((size_t)B, kMaxBlocks)), dim3(kThreads), 0, st,
                      (const double*)sums, grad_f0, p);
   return check_launch();
 }
@@ -799,7 +849,7 @@ extern "C" int ddsp_exp_decay_ir_f32(const float* gain, const float* decay, cons
                                      int L, unsigned flags, void* stream) {
   if (!gain || !decay || !noise || !ir) return DDSP_ERR_NULL_POINTER;
   if (B <= 0 || L <= 0) return DDSP_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(exp_decay_ir_kernel, dim3(grid_for((size_t)B * L)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(exp_decay_ir_kernel, dim3(grid_for((size_t)B * L, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
                      gain, decay, noise, ir, B, L, (flags & DDSP_DECAY_SCALE_EXP_SIGMOID) ? 1 : 0);
   return check_launch();
 }
@@ -821,9 +871,9 @@ extern "C" int ddsp_exp_decay_ir_backward_f32(const float* gain, const float* de
   double* partial = (double*)workspace;
   hipStream_t st = (hipStream_t)stream;
   const int scale = (flags & DDSP_DECAY_SCALE_EXP_SIGMOID) ? 1 : 0;
-  hipLaunchKernelGGL(exp_decay_bwd_partial_kernel, dim3(grid_for((size_t)B * kDecayPartials)), dim3(kThreads), 0,
+  hipLaunchKernelGGL(exp_decay_bwd_partial_kernel, dim3(grid_for((size_t)B * kDecayPartials, kMaxBlocks)), dim3(kThreads), 0,
                      st, decay, noise, grad_ir, partial, B, L);
-  hipLaunchKernelGGL(exp_decay_bwd_finish_kernel, dim3(grid_for((size_t)B)), dim3(kThreads), 0, st, gain, decay,
+  hipLaunchKernelGGL(exp_decay_bwd_finish_kernel, dim3(grid_for((size_t)B, kMaxBlocks)), dim3(kThreads), 0, st, gain, decay,
                      (const double*)partial, grad_gain, grad_decay, B, scale);
   return check_launch();
 }
@@ -912,7 +962,7 @@ extern "C" int ddsp_safe_divide_f32(const float* numerator, const float* denomin
   if (!numerator || !denominator || !out) return DDSP_ERR_NULL_POINTER;
   if (C <= 0 || (den_cols != 1 && den_cols != C)) return DDSP_ERR_BAD_SHAPE;
   if (rows == 0) return DDSP_OK;
-  hipLaunchKernelGGL(safe_divide_kernel, dim3(grid_for(rows * (size_t)C)), dim3(kThreads), 0, (hipStream_t)stream, numerator,
+  hipLaunchKernelGGL(safe_divide_kernel, dim3(grid_for(rows * (size_t)C, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, numerator,
                      denominator, out, rows * (size_t)C, C, den_cols, eps);
   return check_launch();
 }
@@ -920,7 +970,7 @@ extern "C" int ddsp_safe_divide_f32(const float* numerator, const float* denomin
 extern "C" int ddsp_safe_log_f32(const float* x, float* out, size_t n, float eps, void* stream) {
   if (!x || !out) return DDSP_ERR_NULL_POINTER;
   if (n == 0) return DDSP_OK;
-  hipLaunchKernelGGL(safe_log_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, x, out, n, eps);
+  hipLaunchKernelGGL(safe_log_kernel, dim3(grid_for(n, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, x, out, n, eps);
   return check_launch();
 }
 
@@ -928,7 +978,7 @@ extern "C" int ddsp_harmonic_frequencies_f32(const float* frequencies, float* ou
   if (!frequencies || !out) return DDSP_ERR_NULL_POINTER;
   if (n_harmonics <= 0) return DDSP_ERR_BAD_SHAPE;
   if (rows == 0) return DDSP_OK;
-  hipLaunchKernelGGL(harmonic_frequencies_kernel, dim3(grid_for(rows * (size_t)n_harmonics)), dim3(kThreads), 0,
+  hipLaunchKernelGGL(harmonic_frequencies_kernel, dim3(grid_for(rows * (size_t)n_harmonics, kMaxBlocks)), dim3(kThreads), 0,
                      (hipStream_t)stream, frequencies, out, rows, n_harmonics);
   return check_launch();
 }
@@ -938,7 +988,7 @@ extern "C" int ddsp_remove_above_nyquist_f32(const float* frequency_envelopes, c
   if (!frequency_envelopes || !amplitude_envelopes || !out) return DDSP_ERR_NULL_POINTER;
   if (!(sample_rate > 0.0f)) return DDSP_ERR_BAD_SHAPE;
   if (n == 0) return DDSP_OK;
-  hipLaunchKernelGGL(remove_above_nyquist_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(remove_above_nyquist_kernel, dim3(grid_for(n, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
                      frequency_envelopes, amplitude_envelopes, out, n, (float)((double)sample_rate / 2.0));
   return check_launch();
 }
@@ -966,14 +1016,14 @@ extern "C" int ddsp_angular_cumsum_f32(const float* angular_frequency, float* ou
 extern "C" int ddsp_sigmoid_f32(const float* in, float* out, size_t n, void* stream) {
   if (!in || !out) return DDSP_ERR_NULL_POINTER;
   if (n == 0) return DDSP_OK;
-  hipLaunchKernelGGL(sigmoid_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, in, out, n);
+  hipLaunchKernelGGL(sigmoid_kernel, dim3(grid_for(n, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, in, out, n);
   return check_launch();
 }
 
 extern "C" int ddsp_sigmoid_backward_f32(const float* in, const float* grad_out, float* grad_in, size_t n, void* stream) {
   if (!in || !grad_out || !grad_in) return DDSP_ERR_NULL_POINTER;
   if (n == 0) return DDSP_OK;
-  hipLaunchKernelGGL(sigmoid_backward_kernel, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, in, grad_out, grad_in, n);
+  hipLaunchKernelGGL(sigmoid_backward_kernel, dim3(grid_for(n, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, in, grad_out, grad_in, n);
   return check_launch();
 }
 
@@ -982,7 +1032,7 @@ extern "C" int ddsp_mix_backward_f32(const float* signal_one, const float* signa
   if (!signal_one || !signal_two || !mix_level || !grad_out) return DDSP_ERR_NULL_POINTER;
   if (C <= 0) return DDSP_ERR_BAD_SHAPE;
   if (rows == 0 || (!grad_one && !grad_two && !grad_level)) return DDSP_OK;
-  hipLaunchKernelGGL(mix_backward_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, (hipStream_t)stream, signal_one, signal_two,
+  hipLaunchKernelGGL(mix_backward_kernel, dim3(grid_for(rows, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, signal_one, signal_two,
                      mix_level, grad_out, grad_one, grad_two, grad_level, rows, C);
   return check_launch();
 }
@@ -992,7 +1042,7 @@ extern "C" int ddsp_mix_f32(const float* signal_one, const float* signal_two, co
   if (!signal_one || !signal_two || !mix_level || !out) return DDSP_ERR_NULL_POINTER;
   if (C <= 0) return DDSP_ERR_BAD_SHAPE;
   if (rows == 0) return DDSP_OK;
-  hipLaunchKernelGGL(mix_kernel, dim3(grid_for(rows * (size_t)C)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(mix_kernel, dim3(grid_for(rows * (size_t)C, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
                      signal_one, signal_two, mix_level, out, rows, C);
   return check_launch();
 }

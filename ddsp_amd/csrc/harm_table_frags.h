@@ -15,6 +15,7 @@
 #pragma once
 #include <cmath>
 #include <cstring>
+#include "split_f16.h"      // kLoScale: the split these fragments are pre-computed in
 
 namespace ddsp {
 
@@ -61,7 +62,7 @@ inline void wt_frag_element(int T, int n, int k, const float* invpsi512, int n_i
   const double s = sin(2.0 * 3.14159265358979323846264338327950288 * (double)q / (double)(2 * T));
   const float x = (float)((double)(float)s * (double)invpsi512[i]);
   *hi = wt_f16_bits(x);
-  *lo = wt_f16_bits((x - wt_f16_value(*hi)) * 2048.0f);        // (exact in fp32: x has 24 bits, hi its leading 11)
+  *lo = wt_f16_bits((x - wt_f16_value(*hi)) * kLoScale);        // (exact in fp32: x has 24 bits, hi its leading 11)
 }
 inline void wt_fill_frag_set(WtFragSet* f, const float* invpsi512, int n_invpsi) {
   memset(f, 0, sizeof(*f));

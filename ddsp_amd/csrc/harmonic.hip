@@ -27,6 +27,7 @@
 #include "harmonic_table.h"
 #include "filtered_noise_general.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -350,7 +351,6 @@ __global__ __launch_bounds__(kSynthThreads) void harm_synth_kernel(
     }
   }
 }
-
 
 // ------------------------------------------------------------------------------------
 // kernel 3 (the fast path, hop % 64 == 0): controls + phase prefix + synthesis in ONE launch.
@@ -748,8 +748,6 @@ __global__ __launch_bounds__(256, 8) void harm_fused_kernel(
 // =====================================================================================
 using namespace ddsp;
 
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
-
 constexpr int kFusedMaxBlocks = 256 * 8;     // persistent grid: 8 blocks of 256 threads per CU
 // workspace = [ theta0: B*F doubles ][ ws_a: B*(F+1)*Kp floats ]  (two-kernel path), or one
 // 17-row slot per persistent block (fused path)
@@ -1027,7 +1025,6 @@ extern "C" int ddsp_harmonic_streaming_f32(const float* amplitudes, const float*
 namespace ddsp {
 
 constexpr int kBwdMaxHop = 2048;
-
 
 // A block takes `fb` consecutive frames of one row (fb * hop <= kBwdMaxHop samples staged at once):
 // 32000 two-wavefront blocks of one frame each were bound by the block launch rate.

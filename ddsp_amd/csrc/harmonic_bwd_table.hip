@@ -39,10 +39,12 @@
 #include <vector>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "split_f16.h"
 #include "wavetable_coeffs.h"
 #include "harm_table_frags.h"
 #include "profile.h"
 #include "harmonic_bwd_table.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -51,11 +53,6 @@ constexpr int kBtT = 512;
 constexpr int kBtFrames = 8;                 // frames = wavefronts per block
 constexpr int kBtCol = 136;                  // halves per column of a folded plane: 128 + 8 (columns 68 dwords apart)
 constexpr int kBtMaxCross = 8;
-constexpr float kBtLoScale = 2048.0f;
-
-typedef _Float16 bt_f16x8 __attribute__((ext_vector_type(8)));
-typedef float bt_f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t bt_u32x4 __attribute__((ext_vector_type(4)));
 
 struct BtArgs {
   const float* f0;             // [B, F]
@@ -63,7 +60,7 @@ struct BtArgs {
   const float* g;              // [B, N]: dL / d audio
   float* pq;                   // P at 0, Q at q_offset: [B F, K] each
   size_t q_offset;
-  const bt_u32x4* frags;       // [parity][harmonic tile][k-step][hi / lo][lane]
+  const u32x4* frags;       // [parity][harmonic tile][k-step][hi / lo][lane]
   int F, K, N, hop;
   long rows;                   // B F
   float sample_rate, nyquist;
@@ -91,11 +88,6 @@ template <> struct BtPoly<10> {
 // entry i of a frame's G at slot i ^ (block index of 32): a permutation inside every block of 32 entries
 __device__ __forceinline__ int bt_swz(int i) { return i ^ ((i >> 5) & 15); }
 
-__device__ __forceinline__ void bt_split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)((v - (float)hi) * kBtLoScale);
-}
-
 template <int W>
 __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void harm_bwd_table_kernel(BtArgs p) {
   // 129 .. 200 harmonics (W = 10: BASELINE configs[4]'s shapes): SIXTEEN wavefronts - eight of them spread a frame each as below,
@@ -116,7 +108,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void 
   const int par = wave & 1, mt = wave >> 1;
   const bool has_task = mt < kMt;                               // (wave-uniform)
   const bool has_frame = wave < kBtFrames;
-  bt_u32x4 afr[4][2];
+  u32x4 afr[4][2];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -334,7 +326,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void 
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           _Float16 hi, lo;
-          bt_split(ldexpf(v[h][pa][q], -ge), hi, lo);
+          split(ldexpf(v[h][pa][q], -ge), hi, lo);
           s_b[0][pa][2 * wave + q][n] = hi;
           s_b[1][pa][2 * wave + q][n] = lo;
         }
@@ -345,12 +337,12 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void 
   // ---- 3. D[harmonic][column] = sum_n A[harmonic][n] G_folded[n][column] ------------------------------------------------------------
   if (has_task) {
     const int i16 = lane & 15, g4 = lane >> 4;
-    bt_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const bt_f16x8 bh = *reinterpret_cast<const bt_f16x8*>(&s_b[0][par][i16][32 * ks + 8 * g4]);
-      const bt_f16x8 bl = *reinterpret_cast<const bt_f16x8*>(&s_b[1][par][i16][32 * ks + 8 * g4]);
-      const bt_f16x8 ah = __builtin_bit_cast(bt_f16x8, afr[ks][0]), al = __builtin_bit_cast(bt_f16x8, afr[ks][1]);
+      const f16x8 bh = *reinterpret_cast<const f16x8*>(&s_b[0][par][i16][32 * ks + 8 * g4]);
+      const f16x8 bl = *reinterpret_cast<const f16x8*>(&s_b[1][par][i16][32 * ks + 8 * g4]);
+      const f16x8 ah = __builtin_bit_cast(f16x8, afr[ks][0]), al = __builtin_bit_cast(f16x8, afr[ks][1]);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
       acc_hl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc_hl, 0, 0, 0);
       acc_lh = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc_lh, 0, 0, 0);
@@ -363,7 +355,7 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int k0 = 2 * (16 * mt + 4 * g4 + r) + par;                 // 0-based harmonic index (harmonic k0 + 1)
-        float v = ldexpf(acc[r] + (acc_hl[r] + acc_lh[r]) * (1.0f / kBtLoScale), fge);
+        float v = ldexpf(combine(acc[r], acc_hl[r] + acc_lh[r]), fge);
         if (k0 >= fkN) v = 0.0f;
         else if (k0 >= fkA) v -= s_corr[fr][q][k0 - fkA];
         if (k0 < kOutStride) s_out[i16][k0] = v;
@@ -387,9 +379,9 @@ __global__ __launch_bounds__(W == 10 ? 1024 : 64 * kBtFrames, kBtMinWaves) void 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 // the transposed constant factor: A[k'][n] = sin(2 pi k (n + 1/2) / T) / psi_hat(k / T), k = 2 k' + 1 + parity, as A-fragments:
 // [parity][harmonic tile of 16][k-step of 32 points][hi / lo][lane (i = k' & 15, g)][8 halves: n = 32 ks + 8 g + e]
-static const bt_u32x4* bt_fragments(int W) {
+static const u32x4* bt_fragments(int W) {
   static std::mutex mu;
-  static const bt_u32x4* cache[3][16] = {};
+  static const u32x4* cache[3][16] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   const int wi = W == 6 ? 0 : (W == 8 ? 1 : 2);
@@ -423,7 +415,7 @@ static const bt_u32x4* bt_fragments(int W) {
     (void)hipFree(dptr);
     return nullptr;
   }
-  cache[wi][dev] = (const bt_u32x4*)dptr;
+  cache[wi][dev] = (const u32x4*)dptr;
   return cache[wi][dev];
 }
 
@@ -439,7 +431,7 @@ int launch_harm_bwd_table(const float* f0_hz, const double* theta0, const float*
   // The frame-rate chain rule in the same launch (P and Q kept in LDS) was correct and slower: 60.1 us against 41.6 + 21.2 in two
   // launches at batch 32, 215 against 135 + 66 at batch 128 (profiles/r05_harm_bwd_table.txt).
   const int W = K <= 100 ? 6 : (K <= 128 ? 8 : 10);
-  const bt_u32x4* frags = bt_fragments(W);
+  const u32x4* frags = bt_fragments(W);
   if (!frags) return DDSP_ERR_LAUNCH;
   BtArgs a;
   a.f0 = f0_hz; a.theta0 = theta0; a.g = grad_audio; a.pq = pq; a.q_offset = q_offset; a.frags = frags;
@@ -457,7 +449,7 @@ int launch_harm_bwd_table(const float* f0_hz, const double* theta0, const float*
   if (W == 6) hipLaunchKernelGGL((harm_bwd_table_kernel<6>), grid, dim3(64 * kBtFrames), 0, st, a);
   else if (W == 8) hipLaunchKernelGGL((harm_bwd_table_kernel<8>), grid, dim3(64 * kBtFrames), 0, st, a);
   else hipLaunchKernelGGL((harm_bwd_table_kernel<10>), dim3(std::min<unsigned>(grid.x, (unsigned)n_cu)), dim3(1024), 0, st, a);   // (one block of sixteen wavefronts per CU)
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 }  // namespace ddsp

@@ -31,10 +31,12 @@
 #include <type_traits>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "split_f16.h"
 #include "profile.h"
 #include "harmonic_table.h"
 #include "wavetable_coeffs.h"      // (the window's polynomials: compile-time constants; 1 / psi_hat: host tables for the fragments)
 #include "harm_table_frags.h"
+#include "launch.h"
 #include <mutex>
 
 namespace ddsp {
@@ -60,11 +62,6 @@ constexpr int kWtNT = 4;             // tiles of 64 samples an S-wavefront carri
 // row stride of an amplitude plane (fp16 elements; odd / even harmonics apart): 144 B for two k-steps (K <= 128), 208 B
 // for four (K <= 208: three plane buffers of 136 would not fit the LDS next to the tables; harm_table_frags.h)
 template <int NK> struct WtPlane { static constexpr int PS = NK <= 2 ? 72 : 104; };
-constexpr float kWtLoScale = 2048.0f; // x = hi + lo / 2048 in two fp16 numbers
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));      // what v_cvt_pkrtz_f16_f32 returns
 
 struct ChunkTables {
   double theta[kWtRows], w[kWtRows], dw[kWtRows];
@@ -277,12 +274,12 @@ __device__ __forceinline__ f32x2 wt_pk_fma(f32x2 a, f32x2 b, f32x2 c) {
 __device__ __forceinline__ h16x2 wt_rest_halves(f32x2 c2048, h16x2 h) {
 #if defined(__AMDGCN__)
   h16x2 r;
-  const float m = -kWtLoScale;
+  const float m = -kLoScale;
   __asm__("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=&v"(r) : "v"(h), "v"(m), "v"(c2048[0]));
   __asm__("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(h), "v"(m), "v"(c2048[1]));
   return r;
 #else
-  return (h16x2){(__fp16)fmaf((float)h[0], -kWtLoScale, c2048[0]), (__fp16)fmaf((float)h[1], -kWtLoScale, c2048[1])};
+  return (h16x2){(__fp16)fmaf((float)h[0], -kLoScale, c2048[0]), (__fp16)fmaf((float)h[1], -kLoScale, c2048[1])};
 #endif
 }
 // (int)floor(x) in one instruction
@@ -308,7 +305,7 @@ __device__ __forceinline__ f32x2 wt_pk_minus(f32x2 o, f32x2 zz, f32x2 e) {
 }
 // the four 16-byte loads of a k-step have landed when at most N younger loads are still in flight (loads return in order)
 template <int N>
-__device__ __forceinline__ void wt_frags_landed(ddsp_f32x4& a, ddsp_f32x4& b, ddsp_f32x4& c, ddsp_f32x4& d) {
+__device__ __forceinline__ void wt_frags_landed(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
 #if defined(__AMDGCN__)
   __asm__ volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
 #else
@@ -489,7 +486,6 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
     f16x8 ahi[2][2][WIDE ? 1 : NK], alo[2][2][WIDE ? 1 : NK];
     int frag_T = 0;
     auto fetch_fragments = [&](int T) {
-      typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
       const WtFragSet& set = W == 6 ? kWtFragSet6 : kWtFragSet8;
       // (a wave-uniform base and a 32-bit lane offset made HERE: left to itself the compiler keeps a 64-bit address per
       // fragment alive over the whole tick loop - in scratch)
@@ -631,7 +627,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
 #pragma unroll
           for (int rt = 0; rt < kWtRowTiles; ++rt) {
             const _Float16* bsrc = planes_all[pm] + (16 * rt + mi) * kWtPS + 8 * mg;
-            const float am = amp_tab[pm][16 * rt + mi], am_lo = am * (1.0f / kWtLoScale);
+            const float am = amp_tab[pm][16 * rt + mi], am_lo = am * (1.0f / kLoScale);
             f32x4 soe[2];
 #pragma unroll
             for (int par = 0; par < 2; ++par) {
@@ -661,7 +657,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
         const _Float16* bsrc = planes_all[pm] + (16 * rt + mi) * kWtPS + 8 * mg;
         // one parity at a time (four accumulators live, not eight: the constant factor already takes 64 registers)
         f32x4 soe[2][2];                                     // [parity][position tile]: a_j (hi.hi + (hi.lo + lo.hi) / 2048)
-        const float am = amp_tab[pm][16 * rt + mi], am_lo = am * (1.0f / kWtLoScale);      // this lane's table row's amplitude
+        const float am = amp_tab[pm][16 * rt + mi], am_lo = am * (1.0f / kLoScale);      // this lane's table row's amplitude
 #pragma unroll
         for (int par = 0; par < 2; ++par) {
           f32x4 acc[2], accx[2];
@@ -673,7 +669,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
           if constexpr (WIDE) {
             // this parity's sixteen fragments, issued together (pinned: left to itself the compiler hoists these loop-
             // invariant loads out of the tick loop, into registers nobody has) and used k-step by k-step as they land
-            ddsp_f32x4 fr[NK][2][2];                          // [k-step][position tile][hi, lo]
+            f32x4 fr[NK][2][2];                          // [k-step][position tile][hi, lo]
             // (one scalar base per parity, a lane offset per position tile and part, the k-step as the immediate offset;
             // spaced: the bases come back from spill lanes - common.h)
             const char* fbase = reinterpret_cast<const char*>(kWtFragsWide.v) + 16384 * (rw * 2 + par);
@@ -798,8 +794,8 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
               const int k = kA;
               const float kfl = (float)(k + 1);
               const _Float16* pl = planes_all[pm] + ((k & 1) * kWtRows + lane) * kWtPS + (k >> 1);
-              const float c0 = fmaf((float)pl[2 * kWtRows * kWtPS], 1.0f / kWtLoScale, (float)pl[0]);
-              const float c1 = fmaf((float)pl[2 * kWtRows * kWtPS + kWtPS], 1.0f / kWtLoScale, (float)pl[kWtPS]);
+              const float c0 = fmaf((float)pl[2 * kWtRows * kWtPS], 1.0f / kLoScale, (float)pl[0]);
+              const float c1 = fmaf((float)pl[2 * kWtRows * kWtPS + kWtPS], 1.0f / kLoScale, (float)pl[kWtPS]);
               const float top = rn_mul(fj, kfl), bot = rn_mul(fj1, kfl);
               cx = make_float4(rn_mul(c0, amp_tab[pm][lane]), rn_mul(c1, amp_tab[pm][lane + 1]), top, rn_sub(bot, top));
               ck = kfl;
@@ -882,7 +878,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
       // the rows of a chunk in registers: fetched at the top of the tick BEFORE the one that works on them (HBM has a whole
       // tick to answer; fetched at the end of a tick, as in r03h, every tick of the block's slowest wavefronts began
       // with the full latency: 41.0 -> 38.8 us), two sets used in turn (the tick loop is unrolled twice: no copies)
-      struct Rows { ddsp_f32x4 x[NU]; float f0[NU]; };
+      struct Rows { f32x4 x[NU]; float f0[NU]; };
       Rows rows_a, rows_b;
       // (addresses: the clip's first row as wave-uniform bases in scalar registers, the rest as 32-bit byte offsets - a
       // clip's F K floats are < 4 GB and F < 2^24, harm_table_ok: four vector instructions per row pair where 64-bit row
@@ -928,7 +924,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
             load_issue(e2, hb, ro[i] + ku4[2]);
             load_issue(e3, hb, ro[i] + ku4[3]);
             }
-            r.x[i] = (ddsp_f32x4){e0, e1, e2, e3};
+            r.x[i] = (f32x4){e0, e1, e2, e3};
           }
         }
       };
@@ -1019,7 +1015,7 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
 #pragma unroll
           for (int par = 0; par < 2; ++par) {
             const h16x2 hi = __builtin_amdgcn_cvt_pkrtz(c[par][0], c[par][1]);
-            const h16x2 lo = wt_rest_halves(c[par] * kWtLoScale, hi);
+            const h16x2 lo = wt_rest_halves(c[par] * kLoScale, hi);
             if (!WIDE || 2 * hq < kWtPS) {              // (WIDE: a plane row ends at k' = 104; dead harmonics write zeros up to there)
               *reinterpret_cast<h16x2*>(dst + (0 * 2 + par) * kWtRows * kWtPS) = hi;
               *reinterpret_cast<h16x2*>(dst + (1 * 2 + par) * kWtRows * kWtPS) = lo;
@@ -1184,8 +1180,8 @@ __global__ __launch_bounds__(1024) void harm_table_kernel(
                     const float top = fj * kfl, bot = fj1 * kfl;
                     const float fk = rn_add(top, rn_mul(rn_sub(bot, top), lerp[u]));
                     const _Float16* pl = planes + ((k & 1) * kWtRows + q[u]) * kWtPS + (k >> 1);
-                    const float c0 = fmaf((float)pl[2 * kWtRows * kWtPS], 1.0f / kWtLoScale, (float)pl[0]);
-                    const float c1 = fmaf((float)pl[2 * kWtRows * kWtPS + kWtPS], 1.0f / kWtLoScale, (float)pl[kWtPS]);
+                    const float c0 = fmaf((float)pl[2 * kWtRows * kWtPS], 1.0f / kLoScale, (float)pl[0]);
+                    const float c1 = fmaf((float)pl[2 * kWtRows * kWtPS + kWtPS], 1.0f / kLoScale, (float)pl[kWtPS]);
                     const float ak = fmaf(w_next[u], rn_mul(c1, am1), rn_mul(w_cur[u], rn_mul(c0, am0)));
                     const float sv = sin_rev(fmaf(theta[u], kfl, -rintf(theta[u] * kfl)));     // exact fractional part of k theta
                     if (fk >= p.nyquist) out[u] = fmaf(-ak, sv, out[u]);
@@ -1330,7 +1326,7 @@ int launch_harm_table(const float* amplitudes, const float* hd, const float* f0,
 #undef DDSP_LAUNCH_TABLE
 #undef DDSP_LAUNCH_TABLE_
 #undef DDSP_LAUNCH_TABLE__
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 }  // namespace ddsp

@@ -42,6 +42,7 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "common.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace hmm {
@@ -354,11 +355,10 @@ static int make_model(Model* m, size_t rows, int steps, int n_pitches, double ho
   return DDSP_OK;
 }
 
-static int launched() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
-
 }  // namespace hmm
 }  // namespace ddsp
 
+using namespace ddsp;
 using namespace ddsp::hmm;
 
 #define DDSP_HMM_MODEL_PARAMS                                                                                                  \
@@ -376,7 +376,7 @@ extern "C" int ddsp_hmm_log_prob_f32(const float* pitch, const float* amps, floa
     hipLaunchKernelGGL(log_prob_kernel<64>, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, pitch, amps, log_prob, steps, m);
   else
     hipLaunchKernelGGL(log_prob_kernel<256>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, pitch, amps, log_prob, steps, m);
-  return launched();
+  return check_launch();
 }
 
 extern "C" size_t ddsp_hmm_log_prob_backward_workspace_bytes(int rows, int steps, int n_pitches) {
@@ -399,7 +399,7 @@ extern "C" int ddsp_hmm_log_prob_backward_f32(const float* pitch, const float* a
   else
     hipLaunchKernelGGL(log_prob_backward_kernel<256>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, pitch, amps,
                        grad_log_prob, grad_pitch, grad_amps, fwd, steps, m);
-  return launched();
+  return check_launch();
 }
 
 static size_t viterbi_bits_bytes(int rows, int steps, int n_pitches) {
@@ -425,5 +425,5 @@ extern "C" int ddsp_hmm_viterbi_f32(const float* pitch, const float* amps, int* 
   else
     hipLaunchKernelGGL(viterbi_kernel<256>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, pitch, amps, states, bits, args, steps,
                        m);
-  return launched();
+  return check_launch();
 }

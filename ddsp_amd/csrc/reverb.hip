@@ -42,6 +42,7 @@
 #include "profile.h"
 #include "fft_radix8.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -574,7 +575,7 @@ extern "C" int ddsp_fft_convolve_long_ex_f32(const float* audio, const float* im
     hipLaunchKernelGGL(rv_ifft_kernel, dim3((unsigned)(n_items < 2 * n_cu ? n_items : 2 * n_cu)), dim3(kRvThreads), lds, st,
                        (const float2*)xspec, audio, out, p, nbo, j0, n_items);
   }
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 // dL/d ir of a Reverb whose ONE impulse response serves the whole batch (the trainable Reverb: effects.py:62-80): the rows'
@@ -601,7 +602,7 @@ extern "C" int ddsp_sum_rows_f32(const float* x, float* out, int B, int L, int z
   if (B <= 0 || L <= 0) return DDSP_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(ddsp::rv_sum_rows_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out, B, L,
                      zero_first);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_fft_convolve_long_f32(const float* audio, const float* impulse_response,

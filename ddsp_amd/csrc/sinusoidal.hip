@@ -34,6 +34,7 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "profile.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace sinusoidal {
@@ -433,7 +434,6 @@ __global__ __launch_bounds__(kThreads) void sin_bwd_scan_kernel(BwdSums in, floa
   }
 }
 
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
 static inline size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 static inline size_t plane_bytes(int B, int F, int K) { return align_up((size_t)B * F * K * sizeof(float), 16); }
 

@@ -22,6 +22,7 @@
 #include "profile.h"
 #include "fft_radix8.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -1396,7 +1397,7 @@ extern "C" int ddsp_spectral_loss_f32(const float* target_audio, const float* au
                          partial + 2 * (size_t)fin.offset[z], N, frames, fft_sizes[z], 1e-5f);
     }
   hipLaunchKernelGGL(spectral_loss_finish_kernel, dim3(1), dim3(kSlFinishThreads), 0, st, (const double*)partial, loss, fin);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 static int sl_backward_impl(const float* target_audio, const float* audio, const float* grad_loss,
@@ -1448,7 +1449,7 @@ static int sl_backward_impl(const float* target_audio, const float* audio, const
     }
   if (loss)
     hipLaunchKernelGGL(spectral_loss_finish_kernel, dim3(1), dim3(kSlFinishThreads), 0, st, (const double*)partial, loss, fin);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_spectral_loss_backward_f32(const float* target_audio, const float* audio,
@@ -1491,7 +1492,7 @@ extern "C" int ddsp_stft_mag_f32(const float* target_audio, const float* audio, 
       default: return DDSP_ERR_UNSUPPORTED;
     }
 #undef DDSP_SM3_CASE
-    return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+    return check_launch();
   }
   if (!sl_size_ok(fft_size)) return DDSP_ERR_UNSUPPORTED;
   const int S = fft_size, frames = sl_frames(N, S), blocks = sl_blocks(N, S);
@@ -1504,7 +1505,7 @@ extern "C" int ddsp_stft_mag_f32(const float* target_audio, const float* audio, 
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SM_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_stft_mag_backward_f32(const float* audio, const float* grad_mag, float* grad_audio, int B, int N,
@@ -1525,7 +1526,7 @@ extern "C" int ddsp_stft_mag_backward_f32(const float* audio, const float* grad_
       default: return DDSP_ERR_UNSUPPORTED;
     }
 #undef DDSP_SMB3_CASE
-    return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+    return check_launch();
   }
   if (!sl_size_ok(fft_size)) return DDSP_ERR_UNSUPPORTED;
   const int S = fft_size, frames = sl_frames(N, S), blocks = sl_blocks(N, S);
@@ -1538,7 +1539,7 @@ extern "C" int ddsp_stft_mag_backward_f32(const float* audio, const float* grad_
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SMB_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 // ---- |STFT| under a frame geometry of the caller's (spectral_ops.compute_loudness: frames of n_fft = 2048 every sr / 250 = 64
@@ -1566,7 +1567,7 @@ static int sl_frames_mag(const float* audio, float* mag, int B, int N, int fft_s
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SFM_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_stft_frames_mag_f32(const float* audio, float* mag, int B, int N, int fft_size, int hop, int pad_left,
@@ -1596,7 +1597,7 @@ extern "C" int ddsp_stft_frames_f32(const float* audio, float* spectrum, int B, 
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SFC_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_mel_features_f32(const float* audio, const int* bands, const float* weights, const float* dct_t, float* out,
@@ -1622,7 +1623,7 @@ extern "C" int ddsp_mel_features_f32(const float* audio, const int* bands, const
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_MEL_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_stft_frames_mag_backward_f32(const float* audio, const float* grad_mag, float* grad_audio, int B, int N,
@@ -1641,7 +1642,7 @@ extern "C" int ddsp_stft_frames_mag_backward_f32(const float* audio, const float
     default: return DDSP_ERR_UNSUPPORTED;
   }
 #undef DDSP_SFB_CASE
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_loudness_from_mag_f32(const float* mag, const float* weighting, float* loudness, int B, int n_frames,
@@ -1652,7 +1653,7 @@ extern "C" int ddsp_loudness_from_mag_f32(const float* mag, const float* weighti
   p.rows = B * n_frames; p.bins = bins; p.pmin = powf(10.0f, -range_db / 10.0f); p.range_db = range_db; p.ref_db = ref_db;
   hipLaunchKernelGGL(loudness_from_mag_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mag,
                      weighting, loudness, p);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 extern "C" int ddsp_loudness_from_mag_backward_f32(const float* mag, const float* weighting, const float* grad_loudness,
@@ -1664,5 +1665,5 @@ extern "C" int ddsp_loudness_from_mag_backward_f32(const float* mag, const float
   p.rows = B * n_frames; p.bins = bins; p.pmin = powf(10.0f, -range_db / 10.0f); p.range_db = range_db; p.ref_db = ref_db;
   hipLaunchKernelGGL(loudness_from_mag_bwd_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mag,
                      weighting, grad_loudness, grad_mag, p);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }

@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "../../include/ddsp_amd.h"
+#include "launch.h"
 
 namespace ddsp {
 
@@ -280,5 +281,5 @@ extern "C" int ddsp_spectral_terms_f32(const float* target_mag, const float* val
     hipLaunchKernelGGL(spec_terms_grad_kernel, dim3(blocks), dim3(64 * kStRowsPerBlock), lds, st, target_mag, value_mag, weights,
                        (const double*)coef, grad_value_mag, p);
   }
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }

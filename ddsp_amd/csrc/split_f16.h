@@ -1,0 +1,49 @@
+// The split-fp16 operand of the matrix-core kernels: x = hi + lo / 2048, hi and lo two fp16 numbers - 22 bits of x while x is
+// inside fp16's normal range (common.h's pow2_exponent brings data of any scale there first).  A product of two such operands
+// is three MFMAs, hi hi into `acc` and hi lo + lo hi into `cross`, put together by combine().  The parity tolerances rest on
+// this contract, so it is stated here once; the kernels keep only what is theirs (layouts, and forms of the split that are
+// not this one: harmonic_table.hip's wt_rest_halves).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ddsp {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));      // an MFMA A / B fragment of v_mfma_f32_16x16x32_f16
+typedef float f32x4 __attribute__((ext_vector_type(4)));         // its accumulator; four consecutive VGPRs
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));      // (an array of HIP's uint4 - a struct of unions - stays in scratch)
+typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));        // what v_cvt_pkrtz_f16_f32 returns
+
+constexpr float kLoScale = 2048.0f;
+
+// 16 bytes from a 4-byte aligned address
+struct __attribute__((packed, aligned(4))) PackedF4 { float x, y, z, w; };
+struct __attribute__((packed, aligned(4))) PackedU4 { uint32_t x, y, z, w; };
+
+__device__ __forceinline__ void split(float v, _Float16& hi, _Float16& lo) {
+  hi = (_Float16)v;
+  lo = (_Float16)((v - (float)hi) * kLoScale);
+}
+__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    _Float16 h, l;
+    split(v[e], h, l);
+    hi[e] = h;
+    lo[e] = l;
+  }
+}
+// two fp16 numbers as one dword, `a` in the low half
+__device__ __forceinline__ uint32_t pack(_Float16 a, _Float16 b) {
+  return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
+}
+// four such dwords as a fragment
+__device__ __forceinline__ f16x8 frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  const u32x4 v = {a, b, c, d};
+  return __builtin_bit_cast(f16x8, v);
+}
+// the product from its parts: acc = sum hi hi, cross = sum (hi lo + lo hi); float or f32x4
+template <class T>
+__device__ __forceinline__ T combine(T acc, T cross) { return acc + cross * (1.0f / kLoScale); }
+
+}  // namespace ddsp

@@ -38,6 +38,7 @@
 #include "../../include/ddsp_amd.h"
 #include "common.h"
 #include "consistency_common.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace wasserstein {
@@ -244,7 +245,7 @@ static int launch(const float* u_values, const float* v_values, const float* u_w
                   const Args& a, void* stream) {
   hipLaunchKernelGGL((wasserstein_kernel<P, BWD>), dim3((unsigned)rows), dim3(kThreads), 0, (hipStream_t)stream, u_values, v_values,
                      u_weights, v_weights, distance, g_distance, g_u_values, g_v_values, g_u_weights, g_v_weights, a);
-  return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH;
+  return check_launch();
 }
 
 }  // namespace wasserstein

@@ -29,6 +29,7 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "profile.h"
+#include "launch.h"
 
 namespace ddsp {
 namespace wavetable {
@@ -482,7 +483,6 @@ __global__ __launch_bounds__(kThreads) void delay_audio_grad_kernel(const int* _
   gaudio[row + m] = acc;
 }
 
-static inline int check_launch() { return hipGetLastError() == hipSuccess ? DDSP_OK : DDSP_ERR_LAUNCH; }
 static inline size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 static inline unsigned blocks_for(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 

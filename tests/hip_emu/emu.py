@@ -27,8 +27,9 @@ _emu = None
 
 def _digest():
   h = hashlib.sha256()
-  for path in (SOURCE, os.path.join(HERE, 'include', 'hip', 'hip_runtime.h'),
-               os.path.join(ROOT, 'include', 'ddsp_amd.h')):
+  csrc = os.path.dirname(SOURCE)
+  for path in (SOURCE, os.path.join(csrc, 'launch.h'), os.path.join(csrc, 'noise_ir_geom.h'),
+               os.path.join(HERE, 'include', 'hip', 'hip_runtime.h'), os.path.join(ROOT, 'include', 'ddsp_amd.h')):
     with open(path, 'rb') as f:
       h.update(f.read())
   return h.hexdigest()

@@ -6,12 +6,16 @@ each kernel's instruction stream (symbols, labels and comments normalised away) 
 
 Used when an opt-in variant (a new template parameter) is added to a measured kernel: the default instantiation
 must come out instruction for instruction as before, whatever its mangled name now is."""
-import hashlib, json, os, re, subprocess, sys, tempfile
+import hashlib, importlib.util, json, os, re, subprocess, sys, tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'ddsp_amd', 'csrc')
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fno-slp-vectorize', '-I' + os.path.join(ROOT, 'include'),
-         '--cuda-device-only', '-S']
+# the flags the library ships with (ddsp_amd/build.py, loaded by path: the package itself needs torch and the built library)
+_spec = importlib.util.spec_from_file_location('ddsp_amd_build', os.path.join(ROOT, 'ddsp_amd', 'build.py'))
+build = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(build)
+FLAGS = [f for f in build.FLAGS if f not in ('-shared', '-fPIC')] + ['-I' + os.path.join(ROOT, 'include'), '--cuda-device-only', '-S']
 
 
 def demangled_kernels(asm_path):
@@ -30,15 +34,19 @@ def demangled_kernels(asm_path):
 
 def current():
   hashes = {}
+  names = sorted(n for n in os.listdir(CSRC) if n.endswith('.hip'))
   with tempfile.TemporaryDirectory() as tmp:
-    for name in sorted(os.listdir(CSRC)):
-      if not name.endswith('.hip'):
-        continue
+    def compile_one(name):
       asm = os.path.join(tmp, name + '.s')
-      subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + [os.path.join(CSRC, name), '-o', asm], check=True,
-                     stderr=subprocess.DEVNULL)
-      for kernel, h in demangled_kernels(asm).items():
-        hashes['%s: %s' % (name, kernel)] = h
+      cmd = ['/opt/rocm/bin/hipcc'] + FLAGS + build.EXTRA_FLAGS.get(name, []) + [os.path.join(CSRC, name), '-o', asm]
+      done = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+      if done.returncode:
+        sys.exit('%s\n%s' % (' '.join(cmd), done.stderr))
+      return demangled_kernels(asm)
+    with ThreadPoolExecutor(max_workers=min(len(names), os.cpu_count() or 1)) as pool:
+      for name, kernels in zip(names, pool.map(compile_one, names)):
+        for kernel, h in kernels.items():
+          hashes['%s: %s' % (name, kernel)] = h
   return hashes
 
 
