@@ -86,13 +86,15 @@ class Reverb(processors.Processor):
     return core.fft_convolve_long(audio, ir2d, delay=0, add_dry=self._add_dry, mask_tap0=True,
                                   workspace=self._ws)
 
-  def _backward(self, audio, ir2d, grad_out, need_audio, need_ir):
-    """The two correlations of the backward pass, as FFT convolutions with reversed indices."""
+  def _backward(self, audio, ir2d, grad_out, need_audio, need_ir, add_dry=None):
+    """The two correlations of the backward pass, as FFT convolutions with reversed indices.  `add_dry`: the setting the
+    forward pass ran with, as the autograd node took it then (the instance's own when None)."""
+    add_dry = self._add_dry if add_dry is None else add_dry
     g = tf_float32(grad_out)
     n, l = audio.shape[1], ir2d.shape[1]
     grad_audio = grad_ir = None
     if need_audio:       # dL/d audio = reverse(conv(reverse(g), masked ir)[0:N]) (+ g)
-      grad_audio = core.fft_convolve_long(g, ir2d, delay=0, add_dry=self._add_dry, mask_tap0=True,
+      grad_audio = core.fft_convolve_long(g, ir2d, delay=0, add_dry=add_dry, mask_tap0=True,
                                           workspace=self._ws, reverse_audio=True, reverse_out=True)
     if need_ir:          # dL/d ir[k] = conv(g, reverse(audio))[N-1+k]; the masked tap gets none
       # (the masked dry tap gets no gradient: logical output 0 written as zero)
@@ -114,14 +116,14 @@ class _ReverbFunction(torch.autograd.Function):
   def forward(ctx, audio, ir, rev):
     ir2d = rev._ir_2d(ir.detach())
     ctx.save_for_backward(audio, ir2d)
-    ctx.rev, ctx.ir_shape = rev, ir.shape
+    ctx.rev, ctx.ir_shape, ctx.add_dry = rev, ir.shape, bool(rev._add_dry)
     return rev._forward(audio.detach(), ir2d)
 
   @staticmethod
   def backward(ctx, grad_out):
     audio, ir2d = ctx.saved_tensors
     ga, gi = ctx.rev._backward(audio.detach(), ir2d, grad_out, ctx.needs_input_grad[0],
-                               ctx.needs_input_grad[1])
+                               ctx.needs_input_grad[1], ctx.add_dry)
     if gi is not None:
       gi = gi.reshape(ctx.ir_shape)
     return ga, gi, None

@@ -223,9 +223,16 @@ class Harmonic(processors.Processor):
       return dict(signal=audio, controls=controls)
     return audio
 
-  def _backward(self, amplitudes, harmonic_distribution, f0_hz, fuse, grad_audio):
+  def _captured(self, fuse):
+    """The attributes the backward pass reads - (n_samples, sample_rate, amp_resample_method, kernel flags, controls flags) -
+    as the autograd nodes take them in forward: a graph keeps the gradient of the call it recorded when the synth's
+    attributes change before backward()."""
+    return (int(self.n_samples), int(self.sample_rate), self.amp_resample_method, self._flags(fuse),
+            core._harmonic_flags(fuse, self.normalize_below_nyquist, 'window', False))
+
+  def _backward(self, amplitudes, harmonic_distribution, f0_hz, fuse, grad_audio, captured=None):
     b, f, k = harmonic_distribution.shape
-    n = int(self.n_samples)
+    n, sample_rate, _, flags, _ = captured or self._captured(fuse)
     lib = _lib.load()
     dev = amplitudes.device
     grad_audio = core.tf_float32(grad_audio)
@@ -236,29 +243,30 @@ class Harmonic(processors.Processor):
     rc = lib.ddsp_harmonic_backward_f32(
         amplitudes.data_ptr(), harmonic_distribution.data_ptr(), f0_hz.data_ptr(),
         grad_audio.data_ptr(), grad_amp.data_ptr(), grad_hd.data_ptr(), ws.data_ptr(), ws.numel(),
-        b, f, k, n, int(self.sample_rate), self._flags(fuse), 0, core._stream())
+        b, f, k, n, sample_rate, flags, 0, core._stream())
     _lib.check(rc, 'ddsp_harmonic_backward_f32')
     return grad_amp, grad_hd
 
 
-  def _controls(self, amplitudes, harmonic_distribution, f0_hz, fuse):
+  def _controls(self, amplitudes, harmonic_distribution, f0_hz, fuse, captured=None):
     """get_controls on tensors that went through _prescale already (one launch)."""
     b, f, k = harmonic_distribution.shape
+    _, sample_rate, _, _, controls_flags = captured or self._captured(fuse)
     ctl_amp = torch.empty_like(amplitudes)
     ctl_hd = torch.empty_like(harmonic_distribution)
     rc = _lib.load().ddsp_harmonic_controls_f32(
         amplitudes.data_ptr(), harmonic_distribution.data_ptr(), f0_hz.data_ptr(), ctl_amp.data_ptr(),
-        ctl_hd.data_ptr(), b, f, k, int(self.sample_rate),
-        core._harmonic_flags(fuse, self.normalize_below_nyquist, 'window', False), core._stream())
+        ctl_hd.data_ptr(), b, f, k, sample_rate, controls_flags, core._stream())
     _lib.check(rc, 'ddsp_harmonic_controls_f32')
     return {'amplitudes': ctl_amp, 'harmonic_distribution': ctl_hd, 'f0_hz': f0_hz}
 
   def _backward_materialised(self, amplitudes, harmonic_distribution, f0_hz, fuse, grad_audio, want_controls=True,
-                             want_f0=False):
+                             want_f0=False, captured=None):
     """(dL/d amplitudes, dL/d harmonic_distribution, dL/d f0_hz) through the chain of materialised envelopes
     (core.py:1080-1111), the chain's adjoint op for op; the ones not asked for are None."""
     b, f, k = harmonic_distribution.shape
-    n = int(self.n_samples)
+    captured = captured or self._captured(fuse)
+    n, sample_rate, method, _, controls_flags = captured
     lib = _lib.load()
     dev = amplitudes.device
     # This chain holds up to four [batch, n_samples, n_harmonics] fp32 envelopes at once (the reference materialises the same
@@ -269,13 +277,13 @@ class Harmonic(processors.Processor):
     if free_bytes is not None and 4 * envelope_bytes > free_bytes:
       raise MemoryError('Harmonic backward on the materialised-envelope chain (amp_resample_method={!r}, {} harmonics, frames of {} '
                         'samples) needs four [batch={}, n_samples={}, n_harmonics={}] fp32 envelopes = {:.1f} GB; {:.1f} GB are free on '
-                        '{}: split the batch'.format(self.amp_resample_method, k, n // max(f, 1), b, n, k, 4 * envelope_bytes / 1e9,
+                        '{}: split the batch'.format(method, k, n // max(f, 1), b, n, k, 4 * envelope_bytes / 1e9,
                                                      free_bytes / 1e9, dev))
     grad_audio = core.tf_float32(grad_audio)
     # the envelopes the forward pass ran on: f0 [1 .. K] resampled 'linear', amplitudes * distribution resampled by the method
     harmonic_frequencies = torch.empty((b, f, k), dtype=torch.float32, device=dev)
     harmonic_amplitudes = torch.empty((b, f, k), dtype=torch.float32, device=dev)
-    ctl = self._controls(amplitudes, harmonic_distribution, f0_hz, fuse)
+    ctl = self._controls(amplitudes, harmonic_distribution, f0_hz, fuse, captured)
     rc = lib.ddsp_harmonic_envelopes_f32(ctl['amplitudes'].data_ptr(), ctl['harmonic_distribution'].data_ptr(),
                                          f0_hz.data_ptr(), None, harmonic_frequencies.data_ptr(),
                                          harmonic_amplitudes.data_ptr(), b, f, k, core._stream())
@@ -288,28 +296,27 @@ class Harmonic(processors.Processor):
       grad_env = torch.empty((b, n, k), dtype=torch.float32, device=dev)
       rc = lib.ddsp_oscillator_bank_grad_amplitudes_f32(frequency_envelopes.data_ptr(), grad_audio.data_ptr(),
                                                         grad_env.data_ptr(), ws.data_ptr(), ws.numel(), b, n, k,
-                                                        int(self.sample_rate), core._stream())
+                                                        sample_rate, core._stream())
       _lib.check(rc, 'ddsp_oscillator_bank_grad_amplitudes_f32')
       grad_ha = torch.empty((b, f, k), dtype=torch.float32, device=dev)
       rc = lib.ddsp_resample_ex_backward_f32(grad_env.data_ptr(), grad_ha.data_ptr(), b, f, n, k,
-                                             _lib.RESAMPLE_METHODS[self.amp_resample_method], 1, core._stream())
+                                             _lib.RESAMPLE_METHODS[method], 1, core._stream())
       _lib.check(rc, 'ddsp_resample_ex_backward_f32')
       del grad_env
       grad_amp = torch.empty_like(amplitudes)
       grad_hd = torch.empty_like(harmonic_distribution)
       rc = lib.ddsp_harmonic_controls_backward_f32(
           amplitudes.data_ptr(), harmonic_distribution.data_ptr(), f0_hz.data_ptr(), grad_ha.data_ptr(),
-          grad_amp.data_ptr(), grad_hd.data_ptr(), b, f, k, int(self.sample_rate),
-          core._harmonic_flags(fuse, self.normalize_below_nyquist, 'window', False), 0, core._stream())
+          grad_amp.data_ptr(), grad_hd.data_ptr(), b, f, k, sample_rate, controls_flags, 0, core._stream())
       _lib.check(rc, 'ddsp_harmonic_controls_backward_f32')
     if want_f0:
       # dL/d frequency envelopes (a suffix sum over time of dL/d audio A mask cos(phase)), the adjoint of the 'linear'
       # resample, the sum over harmonics weighted [1 .. K]; the frame-rate mask of get_controls (tf.where) passes none
-      amplitude_envelopes = core.resample(harmonic_amplitudes, n, method=self.amp_resample_method)
+      amplitude_envelopes = core.resample(harmonic_amplitudes, n, method=method)
       grad_fenv = torch.empty((b, n, k), dtype=torch.float32, device=dev)
       rc = lib.ddsp_oscillator_bank_grad_frequencies_f32(
           frequency_envelopes.data_ptr(), amplitude_envelopes.data_ptr(), grad_audio.data_ptr(), grad_fenv.data_ptr(),
-          ws.data_ptr(), ws.numel(), b, n, k, int(self.sample_rate), core._stream())
+          ws.data_ptr(), ws.numel(), b, n, k, sample_rate, core._stream())
       _lib.check(rc, 'ddsp_oscillator_bank_grad_frequencies_f32')
       del amplitude_envelopes
       grad_hf = torch.empty((b, f, k), dtype=torch.float32, device=dev)
@@ -322,10 +329,10 @@ class Harmonic(processors.Processor):
       _lib.check(rc, 'ddsp_harmonic_frequencies_backward_f32')
     return grad_amp, grad_hd, grad_f0
 
-  def _backward_f0(self, amplitudes, harmonic_distribution, f0_hz, fuse, grad_audio):
+  def _backward_f0(self, amplitudes, harmonic_distribution, f0_hz, fuse, grad_audio, captured=None):
     """dL/d f0_hz [B,F,1]: the controls once more (one small launch), then ddsp_harmonic_f0_grad_f32."""
     b, f, k = harmonic_distribution.shape
-    n = int(self.n_samples)
+    n, sample_rate, method, _, controls_flags = captured or self._captured(fuse)
     lib = _lib.load()
     dev = amplitudes.device
     grad_audio = core.tf_float32(grad_audio)
@@ -333,15 +340,14 @@ class Harmonic(processors.Processor):
     ctl_hd = torch.empty_like(harmonic_distribution)
     rc = lib.ddsp_harmonic_controls_f32(
         amplitudes.data_ptr(), harmonic_distribution.data_ptr(), f0_hz.data_ptr(), ctl_amp.data_ptr(),
-        ctl_hd.data_ptr(), b, f, k, int(self.sample_rate),
-        core._harmonic_flags(fuse, self.normalize_below_nyquist, 'window', False), core._stream())
+        ctl_hd.data_ptr(), b, f, k, sample_rate, controls_flags, core._stream())
     _lib.check(rc, 'ddsp_harmonic_controls_f32')
     grad_f0 = torch.empty_like(f0_hz)
     ws = self._ws_bwd.get(core.cached_workspace_bytes('ddsp_harmonic_f0_grad_workspace_bytes', b, f, k, n), dev)
     rc = lib.ddsp_harmonic_f0_grad_f32(
         ctl_amp.data_ptr(), ctl_hd.data_ptr(), f0_hz.data_ptr(), grad_audio.data_ptr(), grad_f0.data_ptr(),
-        ws.data_ptr(), ws.numel(), b, f, k, n, int(self.sample_rate),
-        _lib.HARM_AMP_LINEAR if self.amp_resample_method == 'linear' else 0, core._stream())
+        ws.data_ptr(), ws.numel(), b, f, k, n, sample_rate,
+        _lib.HARM_AMP_LINEAR if method == 'linear' else 0, core._stream())
     _lib.check(rc, 'ddsp_harmonic_f0_grad_f32')
     return grad_f0
 
@@ -359,7 +365,7 @@ class _HarmonicMaterialisedFunction(torch.autograd.Function):
   @staticmethod
   def forward(ctx, amplitudes, harmonic_distribution, f0_hz, synth, fuse):
     ctx.save_for_backward(amplitudes, harmonic_distribution, f0_hz)
-    ctx.synth, ctx.fuse = synth, fuse
+    ctx.synth, ctx.fuse, ctx.captured = synth, fuse, synth._captured(fuse)
     with torch.no_grad():
       controls = synth._controls(amplitudes.detach(), harmonic_distribution.detach(), f0_hz.detach(), fuse)
       signal = synth.get_signal(**controls)
@@ -371,7 +377,7 @@ class _HarmonicMaterialisedFunction(torch.autograd.Function):
     amplitudes, harmonic_distribution, f0_hz = (t.detach() for t in ctx.saved_tensors)
     grad_amp, grad_hd, grad_f0 = ctx.synth._backward_materialised(
         amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio,
-        ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.captured)
     return grad_amp, grad_hd, grad_f0, None, None
 
 
@@ -388,17 +394,18 @@ class _HarmonicAddFunction(torch.autograd.Function):
     if audio is None:
       raise _FusedAddUnsupported()
     ctx.save_for_backward(amplitudes, harmonic_distribution, f0_hz)
-    ctx.synth, ctx.fuse = synth, fuse
+    ctx.synth, ctx.fuse, ctx.captured = synth, fuse, synth._captured(fuse)
     return audio
 
   @staticmethod
   def backward(ctx, grad_audio):
     amplitudes, harmonic_distribution, f0_hz = (t.detach() for t in ctx.saved_tensors)
     grad_amp = grad_hd = grad_f0 = None
+    captured = getattr(ctx, 'captured', None)          # (a hand-made context without it: the synth's attributes as they are now)
     if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-      grad_amp, grad_hd = ctx.synth._backward(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio)
+      grad_amp, grad_hd = ctx.synth._backward(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio, captured)
     if ctx.needs_input_grad[2]:
-      grad_f0 = ctx.synth._backward_f0(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio)
+      grad_f0 = ctx.synth._backward_f0(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio, captured)
     return grad_amp, grad_hd, grad_f0, (grad_audio if ctx.needs_input_grad[3] else None), None, None
 
 
@@ -408,7 +415,7 @@ class _HarmonicFunction(torch.autograd.Function):
   @staticmethod
   def forward(ctx, amplitudes, harmonic_distribution, f0_hz, synth, fuse, want_controls):
     ctx.save_for_backward(amplitudes, harmonic_distribution, f0_hz)
-    ctx.synth, ctx.fuse = synth, fuse
+    ctx.synth, ctx.fuse, ctx.captured = synth, fuse, synth._captured(fuse)
     out = synth._forward(amplitudes.detach(), harmonic_distribution.detach(), f0_hz.detach(), fuse, want_controls)
     if not want_controls:
       empty = amplitudes.new_empty(0)
@@ -423,10 +430,11 @@ class _HarmonicFunction(torch.autograd.Function):
     amplitudes, harmonic_distribution, f0_hz = ctx.saved_tensors
     amplitudes, harmonic_distribution, f0_hz = amplitudes.detach(), harmonic_distribution.detach(), f0_hz.detach()
     grad_amp = grad_hd = grad_f0 = None
+    captured = getattr(ctx, 'captured', None)          # (a hand-made context without it: the synth's attributes as they are now)
     if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-      grad_amp, grad_hd = ctx.synth._backward(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio)
+      grad_amp, grad_hd = ctx.synth._backward(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio, captured)
     if ctx.needs_input_grad[2]:
-      grad_f0 = ctx.synth._backward_f0(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio)
+      grad_f0 = ctx.synth._backward_f0(amplitudes, harmonic_distribution, f0_hz, ctx.fuse, grad_audio, captured)
     return grad_amp, grad_hd, grad_f0, None, None, None
 
 
@@ -937,9 +945,13 @@ class FilteredNoise(processors.Processor):
       return dict(signal=audio, controls={'magnitudes': ctl})
     return audio
 
-  def _backward(self, magnitudes, noise, seed, grad_audio, fuse_scale):
+  def _captured(self):
+    """(n_samples, window_size, initial_bias, noise_bits) as the autograd node takes them in forward (see Harmonic._captured)."""
+    return int(self.n_samples), int(self.window_size), float(self.initial_bias), int(self.noise_bits)
+
+  def _backward(self, magnitudes, noise, seed, grad_audio, fuse_scale, captured=None):
     b, f, m = magnitudes.shape
-    n = int(self.n_samples)
+    n, window_size, initial_bias, noise_bits = captured or self._captured()
     lib = _lib.load()
     nbytes = core.cached_workspace_bytes('ddsp_filtered_noise_backward_workspace_bytes', b, f, m, n)
     ws = self._ws_bwd.get(nbytes, magnitudes.device)
@@ -948,8 +960,8 @@ class FilteredNoise(processors.Processor):
     rc = lib.ddsp_filtered_noise_backward_f32(
         magnitudes.data_ptr(), noise.data_ptr() if noise is not None else None,
         grad_audio.data_ptr(), grad_mag.data_ptr(), ws.data_ptr(), ws.numel(), b, f, m, n,
-        int(self.window_size), float(self.initial_bias),
-        (_lib.NOISE_SCALE_EXP_SIGMOID if fuse_scale else 0) | (_lib.NOISE_BITS_23 if self.noise_bits == 23 else 0),
+        window_size, initial_bias,
+        (_lib.NOISE_SCALE_EXP_SIGMOID if fuse_scale else 0) | (_lib.NOISE_BITS_23 if noise_bits == 23 else 0),
         seed, 0, core._stream())
     if rc == -3:
       raise NotImplementedError('FilteredNoise backward needs n_samples / n_frames <= 8192, at most 4097 '
@@ -966,12 +978,15 @@ class _FilteredNoiseFunction(torch.autograd.Function):
     if noise is not None:
       noise = core.tf_float32(noise)
     ctx.seed = (synth.seed & 0xFFFFFFFF) | ((synth._calls & 0xFFFFFFFF) << 32)   # what _run is about to use
+    ctx.captured = synth._captured()
     audio, _ = synth._run(magnitudes.detach(), noise, fuse_scale=fuse_scale, want_controls=False)
-    ctx.save_for_backward(magnitudes)
-    ctx.synth, ctx.noise, ctx.fuse_scale = synth, noise, fuse_scale
+    # supplied noise may be the caller's own tensor (tf_float32 hands a contiguous fp32 device tensor back as it is): saved,
+    # so that an in-place write to it before backward() raises as it does for every torch op; None when it is generated
+    ctx.save_for_backward(magnitudes, noise)
+    ctx.synth, ctx.fuse_scale = synth, fuse_scale
     return audio
 
   @staticmethod
   def backward(ctx, grad_audio):
-    (magnitudes,) = ctx.saved_tensors
-    return ctx.synth._backward(magnitudes.detach(), ctx.noise, ctx.seed, grad_audio, ctx.fuse_scale), None, None, None
+    magnitudes, noise = ctx.saved_tensors
+    return ctx.synth._backward(magnitudes.detach(), noise, ctx.seed, grad_audio, ctx.fuse_scale, ctx.captured), None, None, None
