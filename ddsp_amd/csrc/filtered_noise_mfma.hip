@@ -24,9 +24,10 @@
 // one; at 4-byte alignment two ds_read2_b32 cost 1.7x (profiles/r02a_microbench_lds_unaligned.txt).  The reversed noise
 // is therefore kept twice, the second copy shifted by one element, and a row reads the copy its parity selects.
 //
-// One tile = 30 output frames (1920 samples) of one batch row = 32 staged frames (the first two are history).  Persistent
-// blocks of 8 wavefronts, two per CU, walk their tiles with two LDS buffers and one barrier per tile (see the kernel;
-// the numbers in the comments below are for the 16-wavefront build, halve them):
+// One tile = 32 staged frames (2048 samples) of one batch row.  Persistent blocks of 8 wavefronts, two per CU, walk RUNS of
+// consecutive tiles of one row (noise_mfma_plan.h) with two LDS buffers and one barrier per tile.  A run's first tile spends its
+// first two staged frames on history (the taps reach 127 samples back) and has 30 output frames; every later tile of the run
+// takes over the carry of the tile before it and has 32 (see the FIR wavefronts):
 //   wavefronts 0-3 make the NEXT tile: the 32 x 65 magnitudes straight from HBM into B-fragments (no LDS staging),
 //      exp_sigmoid, hi / lo split, 6 MFMAs each against the constant cosine fragments (fp16 hi / lo pairs made at compile
 //      time), window, hi / lo split of the taps into the LDS tap table; and the Philox noise tile (reversed, hi / lo
@@ -45,13 +46,14 @@
 #include "noise_ir65.h"
 #include "profile.h"
 #include "filtered_noise_mfma.h"
+#include "noise_mfma_plan.h"
 #include "launch.h"
 
 namespace ddsp {
 
-// A tile: kMfRows staged frames = kMfRows / 2 pairs; the first pair is only history (the 128 taps reach 127 samples back),
-// the others are output.
-// Block size.  8 wavefronts (4 producers + 4 FIR) on tiles of 30 output frames, TWO blocks per CU: each block has its own
+// A tile: kMfRows staged frames = kMfRows / 2 pairs; in a run's first tile the first pair is only history (the 128 taps reach
+// 127 samples back) and the others are output, in a tile that continues a run all are.
+// Block size.  8 wavefronts (4 producers + 4 FIR) on tiles of 32 staged frames, TWO blocks per CU: each block has its own
 // barrier, so one block's wait at it is the other block's time (13.7 / 39.1 us at batch 32 / 128).  The two blocks of a
 // CU do not advance together - the arbiter prefers the older block's wavefronts: its ticks take 2.8 us, the younger
 // block's 4.5-6 us until the older one is done.  16 wavefronts on tiles of
@@ -61,8 +63,7 @@ constexpr int kMfWaves = 8;
 constexpr int kMfPW = kMfWaves / 2;            // producer wavefronts = FIR wavefronts
 constexpr int kMfRows = 8 * kMfPW;             // staged frames: 2 of history + the tile's (a producer row group = 16 rows
                                                // x 2 tap tiles; an FIR wavefront = 4 pairs = 8 frames): 32
-constexpr int kMfFrames = kMfRows - 2;         // output frames per tile: 30
-constexpr int kMfTile = kMfFrames * 64;        // 1920 output samples per tile
+static_assert(kMfRows == kMfPlanTileFrames, "noise_mfma_plan.h plans tiles of kMfRows staged frames");
 // tap table: a hi plane and a lo plane; per row 16 groups of 8 taps (16 bytes) + one group of zeros that lanes outside the
 // filter's support read.  The 16 lanes of a ds_read_b128 pass read 16 DIFFERENT groups of one row (or the zero group):
 // with 16-byte groups they cover all 64 banks once (32-byte {hi, lo} groups were a 2-way conflict, and the LDS is what
@@ -84,9 +85,16 @@ static_assert(kMfXPlane >= kMfXPairs * 4 && kMfXPlane % 16 == 0 && (2 * kMfXPlan
 // and what the lo planes held is where the scaled magnitudes travel from the noise makers to the designers (MfHandoff).
 constexpr int kMfXOGen = kMfXPlane + 96;
 static_assert(kMfXOGen % 16 == 0 && (kMfXOGen / 4) % 32 == 16 && kMfWaves == 8, "noise plane layout, generated noise");
-template <bool GEN> struct MfX {
-  static constexpr int O = GEN ? kMfXOGen : 2 * kMfXPlane;                // byte offset of copy O's hi plane
-  static constexpr int BYTES = GEN ? kMfXOGen + kMfXPlane : 4 * kMfXPlane;
+// Where the noise comes from.  Supplied: the caller's, at any scale - x_absmax[row] = max |noise[row]| (row_absmax_kernel, a launch
+// ahead of this one) gives the power of two that brings the row to [1/2, 1) before the fp16 split and the outputs back (ADVICE r4;
+// the FIR is linear in the noise).  Gen11: made on chip, 2048 levels (common.h) - every sample an fp16 number, hi planes only.
+// Gen23: made on chip with 23-bit samples (DDSP_NOISE_BITS_23, the Python mirror's default): hi / lo planes and three MFMAs per
+// step as supplied noise has them, but its samples lie in (-1, 1) as they are made - no row maximum, no exponent, no ldexp.
+enum class MfNoise { Supplied, Gen11, Gen23 };
+template <MfNoise SRC> struct MfX {
+  static constexpr bool LO = SRC != MfNoise::Gen11;                       // lo planes
+  static constexpr int O = LO ? 2 * kMfXPlane : kMfXOGen;                 // byte offset of copy O's hi plane
+  static constexpr int BYTES = LO ? 4 * kMfXPlane : kMfXOGen + kMfXPlane;
 };
 // The scaled magnitudes of a tile as the designers' MFMA B-fragments (rows 16 rg + i, bins 16 g .. + 15 split even / odd, hi / lo),
 // bin 64 and the finished tap 32 of every row: written by the noise makers a tile ahead, read by the designers.
@@ -102,15 +110,11 @@ struct MfArgs {
   float bias;
   uint32_t k0, k1;
   uint64_t batch_offset;
-  int tiles_per_row, n_tiles;       // tiles of 62 frames per batch row; B * tiles_per_row
-  FastDiv whole_per_row, fs_div;    // max(tiles_per_row - 1, 1); fs
-  int n_whole;                      // B * (tiles_per_row - 1): the tiles before the rows' last ones
-  // The hi / lo instances (GEN_NOISE = false) serve two callers.  Noise the caller SUPPLIES comes at any scale: x_absmax[row] =
-  // max |noise[row]| (row_absmax_kernel, a launch ahead of this one) gives the power of two that brings the row to [1/2, 1)
-  // before the fp16 split and the outputs back (the FIR is linear in the noise).  And DDSP_NOISE_BITS_23: x == null,
-  // the noise is generated on chip with 23-bit samples (common.h), which need the hi / lo pair as supplied noise does.
-  const float* x_absmax;
-  int bits23;
+  // the run plan (noise_mfma_plan.h): n_runs runs of run_len consecutive tiles each, runs_per_row of them per batch row, run r of a
+  // row starting at output frame run_frames r of it; dealt to the blocks round-robin, the rows' last runs (ids n_whole ..) last
+  int run_len, run_frames, runs_per_row, n_runs, n_whole;
+  FastDiv run_len_div, whole_per_row_div, fs_div;       // run_len; max(runs_per_row - 1, 1); fs
+  const float* x_absmax;            // supplied noise: the rows' max |noise| (MfNoise)
 };
 
 static __constant__ Ir65Frags kIr65Frags = make_ir65_frags();
@@ -167,23 +171,21 @@ __device__ __forceinline__ void mf_put_quad(float4 v, int qd, unsigned char* s_x
   }
 }
 
-// The noise tile x[z0-128 .. z0+128+kMfTile) into the LDS planes (reversed, two copies): NLANES lanes (ltid).  Supplied noise:
+// The noise tile x[zs .. zs + 64 kMfRows) into the LDS planes (reversed, two copies): NLANES lanes (ltid).  Supplied noise:
 // 16 kMfRows / NLANES quads of four samples per lane, hi / lo split.  Generated noise (common.h: 2048 levels, every value an fp16
 // number): 8 kMfRows / NLANES octets per lane - a Philox block is eight samples -, hi planes only.
-template <bool GEN_NOISE, int NLANES>
-__device__ __forceinline__ void mf_noise_tile(int ltid, int b, int z0, const float* __restrict__ x, unsigned char* s_xe,
+template <MfNoise SRC, int NLANES>
+__device__ __forceinline__ void mf_noise_tile(int ltid, int b, int zs, const float* __restrict__ x, unsigned char* s_xe,
                                               unsigned char* s_xo, const MfArgs& p) {
   // supplied noise: the exponent of the row's largest magnitude (a scalar load: the row is wave-uniform)
   int x_exp = 0;
-  if constexpr (!GEN_NOISE) {
-    if (p.x_absmax) x_exp = pow2_exponent(p.x_absmax[b]);
-  }
-  if constexpr (GEN_NOISE) {
+  if constexpr (SRC == MfNoise::Supplied) x_exp = pow2_exponent(p.x_absmax[b]);
+  if constexpr (SRC == MfNoise::Gen11) {
     static_assert((8 * kMfRows) % NLANES == 0, "octets per lane");
 #pragma unroll
     for (int h = 0; h < 8 * kMfRows / NLANES; ++h) {
       const int oc = ltid + NLANES * h;
-      const int i = z0 - 128 + 8 * oc;                              // a multiple of 8 (z0 is a multiple of 64)
+      const int i = zs + 8 * oc;                                    // a multiple of 8 (zs is a multiple of 64)
       float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
       if (i >= 0 && i < p.N) {                                       // (i < 0: i <= -8, the whole octet lies before the clip)
         const U4 r = noise_philox(U4{(uint32_t)(i >> 3), (uint32_t)(p.batch_offset + b), 0u, 0u}, p.k0, p.k1);
@@ -207,10 +209,10 @@ __device__ __forceinline__ void mf_noise_tile(int ltid, int b, int z0, const flo
 #pragma unroll
     for (int h = 0; h < 16 * kMfRows / NLANES; ++h) {
       const int qd = ltid + NLANES * h;
-      const int i = z0 - 128 + 4 * qd;
+      const int i = zs + 4 * qd;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (i >= 0 && i < p.N) {
-        if (x == nullptr) {                                          // (launch-uniform) 23-bit samples made here
+        if constexpr (SRC == MfNoise::Gen23) {                       // 23-bit samples made here
           v = noise_quad_at((uint32_t)i, p.batch_offset + b, p.k0, p.k1, true);
           if (i + 1 >= p.N) v.y = 0.f;
           if (i + 2 >= p.N) v.z = 0.f;
@@ -244,34 +246,42 @@ __device__ __forceinline__ void mf_noise_tile(int ltid, int b, int z0, const flo
 //               SIMD a pair took 1400 clocks, profiles/r02e_noise_mfma_v3_persistent_12waves.txt).
 // The producers fetch the magnitudes of tile k+2 at the top of the tick and use them a tick later, so no wavefront
 // ever waits for HBM.
-template <bool GEN_NOISE, bool FS64>
+template <MfNoise SRC, bool FS64>
 __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     const float* __restrict__ mag /*[B,F,65]*/, const float* __restrict__ x /*[B,N] or null*/,
     float* __restrict__ ctl_out /*[B,F,65] or null*/, float* __restrict__ out /*[B,N]*/, MfArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char s_taps_all[2][2 * kMfTapPlane];       // hi plane, lo plane
-  constexpr int kXO = MfX<GEN_NOISE>::O;             // copy O's hi plane (its lo plane, supplied noise only: + kMfXPlane)
-  __shared__ __attribute__((aligned(16))) unsigned char s_x_all[2][MfX<GEN_NOISE>::BYTES];      // planes E hi, [E lo,] O hi [, O lo]
+  constexpr bool GEN_NOISE = SRC == MfNoise::Gen11;   // hi planes only, and the handoff in what the lo planes held
+  constexpr bool SUPPLIED = SRC == MfNoise::Supplied;
+  constexpr int kXO = MfX<SRC>::O;             // copy O's hi plane (its lo plane, supplied noise only: + kMfXPlane)
+  __shared__ __attribute__((aligned(16))) unsigned char s_x_all[2][MfX<SRC>::BYTES];      // planes E hi, [E lo,] O hi [, O lo]
   __shared__ __attribute__((aligned(16))) std::conditional_t<GEN_NOISE, MfHandoff, uint4> s_hand[2];      // (generated noise: see the producers)
-  __shared__ __attribute__((aligned(16))) float s_carry[2][kMfPW - 1][128];       // right halves handed from FIR wavefront w to w + 1
+  // right halves handed from FIR wavefront w to w + 1, and from the last one to wavefront 0 of the run's next tile
+  __shared__ __attribute__((aligned(16))) float s_carry[2][kMfPW][128];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mi = lane & 15, mg = lane >> 4;            // MFMA fragment coordinates
-  const int n_my = (p.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;     // tiles of this block
-  // tile T -> (batch row, tile tx of the row): first output z0 = 3968 tx (a multiple of 64); tap rows: frames f_first ..
-  // f_first + 63 (frames of the inputs x[z0-128 ..]); negative for the first tile.  The rows' LAST tiles come last in the
-  // order (T >= n_whole): they are mostly beyond the end of the row (a 4 s clip is 16.1 tiles) and cost a fraction of a
-  // tick, so that a block's longest schedule is 8 whole tiles + 1 short one at batch 128 (2 + 1 at batch 32), not 9 (3).
+  // tiles of this block: its runs (blockIdx, blockIdx + grid, ...) of run_len tiles each, one after the other
+  const int n_my = p.run_len * ((p.n_runs - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x);
+  // The block's tile number t -> tile j of its run t / run_len -> (batch row, run of the row).  A run's first tile (j = 0) stages two
+  // frames of history ahead of its 30 output frames: its first staged sample zs lies 128 before its first output.  Every later tile
+  // CONTINUES the run (cont): it stages 32 output frames, zs is its first output, and what the previous tile's last pair spilled
+  // over its end - the carry into pair 0 - waits in s_carry.  zs is a multiple of 64 (-128 at the start of a row).  Tap rows:
+  // frames f_first .. (the frames of the inputs x[zs ..]); rel0: where zs lies in frame f_first.  Tiles past the end of the row
+  // (the plan's rounding) cost a fraction of a tick: nothing to scale, design or filter.
   // (divisions by launch constants: fastdiv, common.h)
-#define DDSP_MF_TILE(T, b_, z0_, ffirst_, rel0_)                                                        \
-  const bool last_ = (T) >= p.n_whole;                                                                  \
-  uint32_t tx_;                                                                                         \
-  const int bq_ = (int)fastdiv((uint32_t)(T), p.whole_per_row, tx_);                                    \
-  const int b_ = last_ ? (T) - p.n_whole : bq_;                                                         \
-  const int z0_ = (last_ ? p.tiles_per_row - 1 : (int)tx_) * kMfTile;                                   \
+#define DDSP_MF_TILE(t, b_, zs_, cont_, ffirst_, rel0_)                                                 \
+  uint32_t j_, rw_;                                                                                     \
+  const int run_ = (int)blockIdx.x + (int)fastdiv((uint32_t)(t), p.run_len_div, j_) * (int)gridDim.x;   \
+  const bool last_ = run_ >= p.n_whole;                                                                 \
+  const int bq_ = (int)fastdiv((uint32_t)run_, p.whole_per_row_div, rw_);                               \
+  const int b_ = last_ ? run_ - p.n_whole : bq_;                                                        \
+  const bool cont_ = j_ != 0u;                                                                          \
+  const int zs_ = 64 * ((last_ ? p.runs_per_row - 1 : (int)rw_) * p.run_frames + 32 * (int)j_ - 2);     \
   uint32_t fr_;                                                                                         \
-  const int fq_ = (int)fastdiv((uint32_t)(z0_ >= 128 ? z0_ - 128 : 128 - z0_ + p.fs - 1), p.fs_div, fr_); \
-  const int ffirst_ = (z0_ >= 128) ? fq_ : -fq_;                                                        \
-  const int rel0_ = (z0_ - 128) - ffirst_ * p.fs
+  const int fq_ = (int)fastdiv((uint32_t)(zs_ >= 0 ? zs_ : -zs_ + p.fs - 1), p.fs_div, fr_);            \
+  const int ffirst_ = (zs_ >= 0) ? fq_ : -fq_;                                                          \
+  const int rel0_ = zs_ - ffirst_ * p.fs
 
   if (wave < kMfPW) {
     // =========================== producer wavefronts ==================================================================
@@ -311,11 +321,11 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // configs[4]) twelve, all in row group 0.  A row group none of whose rows any staged frame reads is neither fetched nor scaled
     // nor designed (until round 4 it was: 130 MB of HBM traffic per launch against 82 algorithmic at that shape, pmc_traffic_config5.json).
     // (the frames a tile owns for the controls output - scale_rows - lie among the rows its taps need or one past them)
-    auto group_unused = [&](int rel0, int z0, int f_first) -> bool {
+    auto group_unused = [&](int rel0, int zs, int f_first) -> bool {
       if (FS64) return false;
       uint32_t r_;
       const int last_tap_row = (int)fastdiv((uint32_t)(rel0 + 64 * (kMfRows - 1)), p.fs_div, r_);
-      const int own_hi = (int)fastdiv((uint32_t)(z0 + kMfTile - 128), p.fs_div, r_) + 2;          // as in scale_rows
+      const int own_hi = (int)fastdiv((uint32_t)(zs + 64 * kMfRows - 128), p.fs_div, r_) + 2;      // as in scale_rows
       return 16 * rg > last_tap_row && 16 * rg >= own_hi - f_first;
     };
     // the 16 bins of this lane's B-fragments (row = 16 rg + i, bins 16 g .. + 15) and bin 64 of that row, straight from
@@ -323,27 +333,30 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     PackedF4 rq[4];
     float r_last;
     auto fetch_rows = [&](int tick_of_tile) {        // the rows of the block's tile number `tick_of_tile` (clamped to its last)
-      const int T = (int)blockIdx.x + min(max(tick_of_tile, 0), n_my - 1) * (int)gridDim.x;
-      DDSP_MF_TILE(T, b, z0, f_first, rel0);
-      if (group_unused(rel0, z0, f_first)) return;     // (wave-uniform)
+      const int t = min(max(tick_of_tile, 0), n_my - 1);
+      DDSP_MF_TILE(t, b, zs, cont, f_first, rel0);
+      (void)cont;
+      if (group_unused(rel0, zs, f_first)) return;     // (wave-uniform)
       const int rfr = f_first + rrow;
       const float* __restrict__ src = mag + ((size_t)b * p.F + ((rfr >= 0 && rfr < p.F) ? rfr : 0)) * 65;
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) rq[c4] = *reinterpret_cast<const PackedF4*>(src + 16 * mg + 4 * c4);
       r_last = src[64];
     };
-    // the fetched rows of tile T scaled, masked and split: the four B-fragments, bin 64, tap 32's value; the controls written.
+    // the fetched rows of the block's tile t scaled, masked and split: the four B-fragments, bin 64, tap 32's value; the controls written.
     // (false: the tile's rows lie past the end of the clip - nobody reads their taps)
-    auto scale_rows = [&](int T, f16x8& be_hi, f16x8& be_lo, f16x8& bo_hi, f16x8& bo_lo, float& m_last, float& t32) -> bool {
-      DDSP_MF_TILE(T, b, z0, f_first, rel0);
-      // controls ownership: tile t writes frames [own_lo, own_hi) so that every frame is written once
-      const int own_lo = (z0 == 0) ? 0 : f_first + 2;
+    auto scale_rows = [&](int t, f16x8& be_hi, f16x8& be_lo, f16x8& bo_hi, f16x8& bo_lo, float& m_last, float& t32) -> bool {
+      DDSP_MF_TILE(t, b, zs, cont, f_first, rel0);
+      // controls ownership: a tile writes frames [own_lo, own_hi) so that every frame is written once: with g(z) = (z - 128) / fs + 2,
+      // own_lo = g(its first output) - 0 at the start of the row - and own_hi = g(the first output after it), the next tile's own_lo
+      // wherever that tile runs.  (A run's first tile: g(zs + 128) = f_first + 2.)
       uint32_t own_r;
-      const int own_hi = (int)fastdiv((uint32_t)(z0 + kMfTile - 128), p.fs_div, own_r) + 2;
+      const int own_lo = (zs < 0) ? 0 : (cont ? (int)fastdiv((uint32_t)(zs - 128), p.fs_div, own_r) : f_first) + 2;
+      const int own_hi = (int)fastdiv((uint32_t)(zs + 64 * kMfRows - 128), p.fs_div, own_r) + 2;
       const int rfr = f_first + rrow;
       const bool rvalid = rfr >= 0 && rfr < p.F;
       // rows past frame F + 1 are read by no FIR wavefront that stores anything (see `active` there): skipped whole
-      if (f_first + 16 * rg > p.F + 1 || group_unused(rel0, z0, f_first)) return false;
+      if (f_first + 16 * rg > p.F + 1 || group_unused(rel0, zs, f_first)) return false;
       float y[16];
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) { y[4 * c4] = rq[c4].x; y[4 * c4 + 1] = rq[c4].y; y[4 * c4 + 2] = rq[c4].z; y[4 * c4 + 3] = rq[c4].w; }
@@ -385,12 +398,11 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // waited for (r05a timeline: designers 1.1 - 1.6 us, FIR 1.7 - 1.9, ticks of 2.6)
     auto make_noise = [&](int tick) {
       if (tick >= 0 && tick + 1 < n_my) {            // (tile 0's noise: the FIR wavefronts, idle in tick -1)
-        const int T = (int)blockIdx.x + (tick + 1) * (int)gridDim.x;
-        DDSP_MF_TILE(T, b, z0, f_first, rel0);
-        (void)rel0; (void)f_first;
+        DDSP_MF_TILE(tick + 1, b, zs, cont, f_first, rel0);
+        (void)rel0; (void)f_first; (void)cont;
         unsigned char* const s_xe = s_x_all[(tick + 1) & 1];
-        if constexpr (HANDOFF) mf_noise_tile<GEN_NOISE, 64 * kMfPW>(tid, b, z0, x, s_xe, s_xe + kXO, p);
-        else mf_noise_tile<GEN_NOISE, 32 * kMfPW>(tid - 32 * kMfPW, b, z0, x, s_xe, s_xe + kXO, p);
+        if constexpr (HANDOFF) mf_noise_tile<SRC, 64 * kMfPW>(tid, b, zs, x, s_xe, s_xe + kXO, p);
+        else mf_noise_tile<SRC, 32 * kMfPW>(tid - 32 * kMfPW, b, zs, x, s_xe, s_xe + kXO, p);
       }
     };
     if (!designer) {
@@ -401,11 +413,10 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
         if constexpr (HANDOFF) {
           // the magnitudes of tile tick + 2, for the designers' next tick
           if (tick + 2 < n_my) {
-            const int T = (int)blockIdx.x + (tick + 2) * (int)gridDim.x;
             MfHandoff& h = s_hand[(tick + 2) & 1];
             f16x8 be_hi, be_lo, bo_hi, bo_lo;
             float m_last, t32;
-            if (scale_rows(T, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) {
+            if (scale_rows(tick + 2, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) {
               h.frag[rg][0][lane] = __builtin_bit_cast(uint4, be_hi);
               h.frag[rg][1][lane] = __builtin_bit_cast(uint4, be_lo);
               h.frag[rg][2][lane] = __builtin_bit_cast(uint4, bo_hi);
@@ -478,16 +489,15 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       auto designer_tick = [&](int tick, auto scale_here_tag) {
         constexpr bool SCALE_HERE = decltype(scale_here_tag)::value;
         if (tick + 1 < n_my) {
-          const int T = (int)blockIdx.x + (tick + 1) * (int)gridDim.x;
           unsigned char* const s_taps = s_taps_all[(tick + 1) & 1];
           if constexpr (SCALE_HERE) {
             f16x8 be_hi, be_lo, bo_hi, bo_lo;
             float m_last = 0.0f, t32 = 0.0f;
-            if (scale_rows(T, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) design_rows(s_taps, be_hi, be_lo, bo_hi, bo_lo, m_last, t32);
+            if (scale_rows(tick + 1, be_hi, be_lo, bo_hi, bo_lo, m_last, t32)) design_rows(s_taps, be_hi, be_lo, bo_hi, bo_lo, m_last, t32);
           } else if constexpr (HANDOFF) {
-            DDSP_MF_TILE(T, b, z0, f_first, rel0);
-            (void)b;
-            if (f_first + 16 * rg <= p.F + 1 && !group_unused(rel0, z0, f_first)) {        // (the noise maker's own test: scale_rows)
+            DDSP_MF_TILE(tick + 1, b, zs, cont, f_first, rel0);
+            (void)b; (void)cont;
+            if (f_first + 16 * rg <= p.F + 1 && !group_unused(rel0, zs, f_first)) {        // (the noise maker's own test: scale_rows)
               const MfHandoff& h = s_hand[(tick + 1) & 1];
               design_rows(s_taps, __builtin_bit_cast(f16x8, h.frag[rg][0][lane]), __builtin_bit_cast(f16x8, h.frag[rg][1][lane]),
                           __builtin_bit_cast(f16x8, h.frag[rg][2][lane]), __builtin_bit_cast(f16x8, h.frag[rg][3][lane]),
@@ -514,13 +524,18 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // With p = c in every lane, B of step c + 1 is B of step c moved ONE column up (a' - p - 1 is what column a - 1 had),
     // zeros entering at column 0: only step 0 reads the tap table, steps 1 .. 4 are 8 DPP moves each (row_shr:1).  The LDS
     // is what bounds the FIR wavefronts; this takes 8 of a pass's 30 reads and 40 % of its bytes away.
-    // Pair P = staged frames 2 P, 2 P + 1; pairs 1 .. 31 are output.  FIR wavefront cw walks the four pairs 4 cw ..
-    // 4 cw + 3 (unrolled: every LDS address is a per-lane register plus an immediate).  Pair 0 only builds the carry
-    // into pair 1 (its own outputs belong to the previous tile).  The left half of wavefront cw >= 1's first pair lacks
-    // what pair 4 cw - 1 spills into it: that right half is left in LDS by wavefront cw - 1 (s_carry), the incomplete
-    // left half stays in registers, and the two are added and stored at the start of the NEXT tick, behind the block's
-    // barrier (a warm-up pair per wavefront instead would be a fifth pass: 25 % more MFMAs and LDS reads, and the LDS is
-    // what bounds this phase).
+    // Pair P = staged frames 2 P, 2 P + 1.  FIR wavefront cw walks the four pairs 4 cw .. 4 cw + 3 (unrolled: every LDS
+    // address is a per-lane register plus an immediate).  In a run's first tile pair 0 only builds the carry into pair 1
+    // (its own outputs belong to whoever runs the frames before) and pairs 1 .. 15 are output; in a tile that continues a
+    // run all sixteen are, and the carry into pair 0 is the right half the previous tile's last wavefront left in s_carry
+    // a tick ago - behind the barrier, so wavefront 0 adds it and stores right away.  The left half of wavefront cw >= 1's
+    // first pair lacks what pair 4 cw - 1 spills into it: that right half is left in LDS by wavefront cw - 1 (s_carry),
+    // the incomplete left half stays in registers, and the two are added and stored at the start of the NEXT tick, behind
+    // the block's barrier (a warm-up pair per wavefront instead would be a fifth pass: 25 % more MFMAs and LDS reads, and
+    // the LDS is what bounds this phase).
+    // ONE order of addition: every output is fma(cross, 1 / 2048, acc) + carry, the carry last, whichever way the carry
+    // came (registers, s_carry between wavefronts, s_carry between tiles): a sample's bits do not depend on where the
+    // wavefront, tile and run boundaries of its row fall, so a row filtered alone equals the same row in any batch.
     const int cw = wave - kMfPW;
     const int p_first = 4 * cw;
     f32x4 kept = {0.f, 0.f, 0.f, 0.f};      // the incomplete left half of this wavefront's first pair (cw >= 1), last tile
@@ -544,7 +559,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       if (cw >= 1 && kept_ot != nullptr && mi < 8) {
         const float4 cr = *reinterpret_cast<const float4*>(&s_carry[parity][cw - 1][lane_off]);
         float v[4] = {kept[0] + cr.x, kept[1] + cr.y, kept[2] + cr.z, kept[3] + cr.w};
-        if constexpr (!GEN_NOISE) {
+        if constexpr (SUPPLIED) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = ldexpf(v[r], kept_exp);
         }
@@ -558,36 +573,37 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
       if (tick >= 1) flush_kept((tick - 1) & 1);
       if (tick < 0) {
         // nothing to filter yet: the noise of the block's first tile, while the producers design its taps
-        const int T = (int)blockIdx.x;
-        DDSP_MF_TILE(T, b, z0, f_first, rel0);
-        (void)f_first; (void)rel0;
-        mf_noise_tile<GEN_NOISE, 64 * kMfPW>(tid - 64 * kMfPW, b, z0, x, s_x_all[0], s_x_all[0] + kXO, p);
+        DDSP_MF_TILE(0, b, zs, cont, f_first, rel0);
+        (void)f_first; (void)rel0; (void)cont;
+        mf_noise_tile<SRC, 64 * kMfPW>(tid - 64 * kMfPW, b, zs, x, s_x_all[0], s_x_all[0] + kXO, p);
       }
       bool active = false;
       if (tick >= 0) {
-        const int T = (int)blockIdx.x + tick * (int)gridDim.x;
-        DDSP_MF_TILE(T, b, z0, f_first, rel0);
-        (void)f_first;
+        DDSP_MF_TILE(tick, b, zs, cont, f_first, rel0);
+        (void)f_first; (void)b; (void)rel0; (void)cont;
         // (a wavefront whose four pairs lie past the end of the row has nothing to store: most of a row's last tile)
-        active = (long)z0 - 128 + 128L * p_first - p.start < (long)p.N;
+        active = (long)zs + 128L * p_first - p.start < (long)p.N;
       }
       if (active) {
-        const int T = (int)blockIdx.x + tick * (int)gridDim.x;
-        DDSP_MF_TILE(T, b, z0, f_first, rel0);
+        DDSP_MF_TILE(tick, b, zs, cont, f_first, rel0);
         (void)f_first;
+        // wavefront 0 of a tile that continues a run: pair 0 is output, its carry is in s_carry already
+        const bool first_direct = cont && cw == 0;
         const unsigned char* const s_taps = s_taps_all[tick & 1];
         const unsigned char* const s_x = s_x_all[tick & 1];
         float* __restrict__ o = out + (size_t)b * p.N;
-        // out index of this lane's first value of pair 8 cw: z = z0 - 128 + 128 P + 16 a + 4 g (+ r)
-        const long n_tile = (long)z0 - 128 + 128L * p_first - p.start;
+        // out index of this lane's first value of pair 4 cw: z = zs + 128 P + 16 a + 4 g (+ r)
+        const long n_tile = (long)zs + 128L * p_first - p.start;
         // every store of this wavefront inside [0, N) and 8-byte aligned: no per-element checks
-        const bool interior = n_tile + 128 >= 0 && n_tile + 128 * 4 <= (long)p.N && (((p.start | p.N) & 1) == 0);
+        const bool interior = n_tile + (first_direct ? 0 : 128) >= 0 && n_tile + 128 * 4 <= (long)p.N && (((p.start | p.N) & 1) == 0);
         float* __restrict__ ot = o + n_tile;                               // wave-uniform base; lanes add a 32-bit offset
         int o_exp = 0;                                                     // supplied noise: its row's exponent back at the stores
-        if constexpr (!GEN_NOISE) {
-          if (p.x_absmax) o_exp = pow2_exponent(p.x_absmax[b]);
-        }
+        if constexpr (SUPPLIED) o_exp = pow2_exponent(p.x_absmax[b]);
         f32x4 carry = {0.f, 0.f, 0.f, 0.f};
+        if (first_direct && mi < 8) {                  // (the previous tick's wavefront kMfPW - 1 was active: it lies before this one)
+          const float4 cr = *reinterpret_cast<const float4*>(&s_carry[(tick - 1) & 1][kMfPW - 1][lane_off]);
+          carry = (f32x4){cr.x, cr.y, cr.z, cr.w};
+        }
         int a_hi[2], a_lo[2], b_ptr = b_ptr0;
         DDSP_KEEP_IN_VGPR(b_ptr);
         __builtin_assume((b_ptr & 15) == 0);
@@ -612,7 +628,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           const int it = j / 5, c = j - 5 * it;
           const PackedU4 qh = *reinterpret_cast<const PackedU4*>(s_x + a_hi[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
           fah[slot] = frag(qh.x, qh.y, qh.z, qh.w);
-          if constexpr (!GEN_NOISE) {           // (generated noise is fp16 as it stands: no lo plane, no lo . hi product)
+          if constexpr (!GEN_NOISE) {           // (2048-level noise is fp16 as it stands: no lo plane, no lo . hi product)
             const PackedU4 ql = *reinterpret_cast<const PackedU4*>(s_x + a_lo[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
             fal[slot] = frag(ql.x, ql.y, ql.z, ql.w);
           }
@@ -662,17 +678,16 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
             if (c < 4) { fbh = column_up(fbh); fbl = column_up(fbl); }      // under the MFMAs
             __builtin_amdgcn_sched_barrier(0);
             if (c == 4) {
-              const f32x4 comb = combine(acc + carry, acc_hl + acc_lh);
+              const f32x4 comb = combine(acc, acc_hl + acc_lh) + carry;          // the carry last: see above
               acc = (f32x4){0.f, 0.f, 0.f, 0.f};
               acc_hl = (f32x4){0.f, 0.f, 0.f, 0.f};
               acc_lh = (f32x4){0.f, 0.f, 0.f, 0.f};
               // D[row b = 4 g + r][col a = i]: columns 0..7 are complete (the first pair's: see above)
-              if (it == 0) {
-                kept = comb;
-              } else if (mi < 8) {
+              if (it == 0) kept = comb;
+              if (mi < 8 && (it > 0 || first_direct)) {
                 const int idx = lane_off + 128 * it;                         // out index n = n_tile + idx
                 f32x4 st4 = comb;
-                if constexpr (!GEN_NOISE) {
+                if constexpr (SUPPLIED) {
 #pragma unroll
                   for (int r = 0; r < 4; ++r) { const float v = comb[r]; st4[r] = ldexpf(v, o_exp); }
                 }
@@ -694,8 +709,8 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
                 const float v = comb[r];
                 carry[r] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x108, 0xF, 0xF, true));
               }
-              // the last pair's right half: the next wavefront's missing part (the last wavefront's lies past the tile)
-              if (it == 3 && cw < kMfPW - 1 && mi >= 8)
+              // the last pair's right half: the next wavefront's missing part (the last wavefront's: of the run's next tile)
+              if (it == 3 && mi >= 8)
                 *reinterpret_cast<float4*>(&s_carry[tick & 1][cw][lane_off - 128]) = make_float4(comb[0], comb[1], comb[2], comb[3]);
             }
           }
@@ -743,22 +758,17 @@ int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audi
                         int N, int start, float initial_bias, int scale, uint64_t seed, uint64_t batch_offset,
                         int bits23, float* row_scratch /* B floats */, hipStream_t st) {
   MfArgs q;
-  q.x_absmax = nullptr; q.bits23 = bits23;
+  q.x_absmax = nullptr;
   if (noise) {
     if (!row_scratch) return DDSP_ERR_WORKSPACE;
     hipLaunchKernelGGL(row_absmax_kernel, dim3((unsigned)B), dim3(1024), 0, st, noise, N, row_scratch);
     q.x_absmax = row_scratch;
   }
-  const bool lo_planes = noise != nullptr || bits23 != 0;          // the hi / lo instances: supplied noise, or 23-bit samples made on chip
   q.N = N; q.F = F; q.start = start; q.bias = initial_bias; q.scale = scale;
   q.fs = (N + F - 1) / F; q.inv_fs = 1.0f / (float)q.fs;
   q.k0 = (uint32_t)seed; q.k1 = (uint32_t)(seed >> 32); q.batch_offset = batch_offset;
-  q.tiles_per_row = (N + start + kMfTile - 1) / kMfTile;
-  q.n_tiles = B * q.tiles_per_row;
-  q.whole_per_row = make_fastdiv((uint32_t)(q.tiles_per_row > 1 ? q.tiles_per_row - 1 : 1));
   q.fs_div = make_fastdiv((uint32_t)q.fs);
-  q.n_whole = B * (q.tiles_per_row - 1);
-  // persistent grid: one block of 12 wavefronts per CU (two LDS buffers of 76 KB)
+  // persistent grid: two blocks of kMfWaves wavefronts per CU (78 KB of LDS each)
   static const int n_cu = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -767,14 +777,28 @@ int launch_noise_mfma65(const float* magnitudes, const float* noise, float* audi
     return v;
   }();
   const int slots = n_cu * (kMfWaves == 16 ? 1 : 2);
-  const dim3 grid((unsigned)(q.n_tiles < slots ? q.n_tiles : slots));
+  // the run plan of this shape (a search over run lengths: kept from one call to the next, a training step repeats its shape)
+  struct PlanKey { int B, F, fs, start, slots; };
+  static thread_local PlanKey plan_key = {0, 0, 0, 0, 0};
+  static thread_local MfRunPlan plan;
+  if (plan_key.B != B || plan_key.F != F || plan_key.fs != q.fs || plan_key.start != start || plan_key.slots != slots) {
+    plan = plan_noise_mfma_runs(B, F, q.fs, start, slots);
+    plan_key = PlanKey{B, F, q.fs, start, slots};
+  }
+  q.run_len = plan.run_len; q.run_frames = plan.run_frames; q.runs_per_row = plan.runs_per_row;
+  q.n_runs = plan.n_runs; q.n_whole = plan.n_whole;
+  q.run_len_div = make_fastdiv((uint32_t)plan.run_len);
+  q.whole_per_row_div = make_fastdiv((uint32_t)(plan.runs_per_row > 1 ? plan.runs_per_row - 1 : 1));
+  const dim3 grid((unsigned)plan.grid);
   hipEvent_t ev0, ev1;
   profile_kernel_events(kNoiseMfma, &ev0, &ev1);
-#define DDSP_LAUNCH_MF(GEN, FS64)                                                                                      \
-  hipExtLaunchKernelGGL((noise_mfma65_kernel<GEN, FS64>), grid, dim3(64 * kMfWaves), 0, st, ev0, ev1, 0, magnitudes, noise, \
+#define DDSP_LAUNCH_MF(SRC, FS64)                                                                                      \
+  hipExtLaunchKernelGGL((noise_mfma65_kernel<MfNoise::SRC, FS64>), grid, dim3(64 * kMfWaves), 0, st, ev0, ev1, 0, magnitudes, noise, \
                         ctl_magnitudes, audio, q)
-  if (q.fs == 64) { if (lo_planes) DDSP_LAUNCH_MF(false, true); else DDSP_LAUNCH_MF(true, true); }
-  else { if (lo_planes) DDSP_LAUNCH_MF(false, false); else DDSP_LAUNCH_MF(true, false); }
+#define DDSP_LAUNCH_MF_SRC(FS64)                                                                                       \
+  do { if (noise) DDSP_LAUNCH_MF(Supplied, FS64); else if (bits23) DDSP_LAUNCH_MF(Gen23, FS64); else DDSP_LAUNCH_MF(Gen11, FS64); } while (0)
+  if (q.fs == 64) DDSP_LAUNCH_MF_SRC(true); else DDSP_LAUNCH_MF_SRC(false);
+#undef DDSP_LAUNCH_MF_SRC
 #undef DDSP_LAUNCH_MF
   return check_launch();
 }
