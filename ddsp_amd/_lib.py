@@ -56,6 +56,16 @@ SIGNATURES = {
     'ddsp_spectral_loss_value_and_grad_f32': (c_int, [c_f32p] * 4 + [c_voidp, c_size_t, c_int, c_int,
                                                                  ctypes.POINTER(c_int), c_int, c_float,
                                                                  c_float, c_voidp]),
+    'ddsp_spectral_loss_grad_workspace_bytes': (c_size_t, [c_int, c_int, ctypes.POINTER(c_int), c_int]),
+    'ddsp_spectral_loss_backward_det_f32': (c_int, [c_f32p] * 4 + [c_int, c_int, ctypes.POINTER(c_int), c_int,
+                                                               c_float, c_float, c_voidp, c_size_t, c_voidp]),
+    'ddsp_spectral_loss_value_and_grad_det_f32': (c_int, [c_f32p] * 4 + [c_voidp, c_size_t, c_int, c_int,
+                                                                     ctypes.POINTER(c_int), c_int, c_float,
+                                                                     c_float, c_voidp, c_size_t, c_voidp]),
+    'ddsp_stft_mag_backward_workspace_bytes': (c_size_t, [c_int] * 3),
+    'ddsp_stft_mag_backward_det_f32': (c_int, [c_f32p] * 3 + [c_voidp, c_size_t] + [c_int] * 3 + [c_voidp]),
+    'ddsp_stft_frames_mag_backward_workspace_bytes': (c_size_t, [c_int] * 6),
+    'ddsp_stft_frames_mag_backward_det_f32': (c_int, [c_f32p] * 3 + [c_voidp, c_size_t] + [c_int] * 6 + [c_voidp]),
     'ddsp_stft_mag_f32': (c_int, [c_f32p] * 4 + [c_int] * 3 + [c_voidp]),
     'ddsp_spectral_terms_workspace_bytes': (c_size_t, [c_int] * 2),
     'ddsp_spectral_terms_f32': (c_int, [c_f32p] * 3 + [c_int] * 3 + [c_f32p, c_voidp, c_f32p, c_voidp, c_size_t] +

@@ -175,8 +175,29 @@ def mean_difference(target, value, loss_type='L1', weights=None):
   return _md_raw(target, value, loss_type, weights, False)[0]
 
 
-class SpectralLoss(Loss):
-  """Multi-scale spectrogram loss (ddsp/losses.py:131-243)."""
+class _TakesDeterministic(type):
+  """SpectralLoss.__init__ keeps the parameter list of the reference's constructor (ddsp/losses.py:140-187; tests/test_host_api.py
+  holds it to that list).  `deterministic` is this library's own, so it is not one of them: the class takes it, by keyword only,
+  when it is called - SpectralLoss(..., deterministic=True) - checks it there and sets it on the new instance."""
+
+  def __call__(cls, *args, deterministic=None, **kwargs):
+    if not (deterministic is None or isinstance(deterministic, bool)):
+      raise ValueError('deterministic must be True, False or None, got {!r}'.format(deterministic))
+    loss = super().__call__(*args, **kwargs)
+    loss.deterministic = deterministic
+    return loss
+
+
+class SpectralLoss(Loss, metaclass=_TakesDeterministic):
+  """Multi-scale spectrogram loss (ddsp/losses.py:131-243).
+
+  deterministic: how dL/d audio adds its overlapping frames.  False: fp32 atomics (the last bits depend on the order the blocks
+  arrive in).  True: every block stores its stretch to a slab of its own and a second kernel adds each sample's few slabs in a
+  fixed order - the scales in the order of `fft_sizes`, within a scale the covering blocks in ascending order, the loudness term
+  last: the same bits run to run, and a row's gradient does not depend on the other rows' data.  Costs a second workspace
+  (74 MB at batch 32 x 64 000 samples with the default sizes).  None (the default): True exactly when
+  torch.are_deterministic_algorithms_enabled() at the time of the call.  The loss VALUE is the same bits either way.
+  A keyword of the call SpectralLoss(..., deterministic=...) only (any other value: ValueError), and a plain attribute afterwards."""
 
   def __init__(self,
                fft_sizes=(2048, 1024, 512, 256, 128, 64),
@@ -189,6 +210,8 @@ class SpectralLoss(Loss):
                loudness_weight=0.0,
                name='spectral_loss'):
     super().__init__(name=name)
+    self.deterministic = None                # (set by the call of the class: _TakesDeterministic)
+    self._grad_ws = core.Workspace()         # the slabs of the deterministic gradient (per device and stream, as _ws)
     self.fft_sizes = fft_sizes
     self.loss_type = loss_type
     self.mag_weight = mag_weight
@@ -236,6 +259,12 @@ class SpectralLoss(Loss):
       return _SpectralLossFunction.apply(target_audio.detach(), audio, self)
     return self._forward(target_audio, audio)
 
+  def _slabs(self):
+    """Whether this call takes the reproducible gradient (the slab kernels + the gather)."""
+    if self.deterministic is None:
+      return bool(torch.are_deterministic_algorithms_enabled())
+    return bool(self.deterministic)
+
   @staticmethod
   def _fused_size(v):
     v = int(v)
@@ -250,6 +279,7 @@ class SpectralLoss(Loss):
       self._split_key = key
     for part in self._split_parts:           # (the weights are plain attributes a caller may change between calls)
       part.mag_weight, part.logmag_weight = self.mag_weight, self.logmag_weight
+      part.deterministic = self.deterministic
     return self._split_parts
 
   @staticmethod
@@ -311,7 +341,12 @@ class SpectralLoss(Loss):
           cot.data_ptr() if want_grad else None, acc.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), b, frames,
           bins, loss_type, *term_w, 1 if z == 0 else 0, core._stream())
       _lib.check(rc, 'ddsp_spectral_terms_f32')
-      if want_grad:
+      if want_grad and self._slabs():
+        slabs = self._grad_ws.get(core.cached_workspace_bytes('ddsp_stft_mag_backward_workspace_bytes', b, n, size), dev)
+        rc = lib.ddsp_stft_mag_backward_det_f32(audio.data_ptr(), cot.data_ptr(), grad_audio.data_ptr(), slabs.data_ptr(),
+                                                slabs.numel(), b, n, size, core._stream())
+        _lib.check(rc, 'ddsp_stft_mag_backward_det_f32')
+      elif want_grad:
         rc = lib.ddsp_stft_mag_backward_f32(audio.data_ptr(), cot.data_ptr(), grad_audio.data_ptr(), b, n, size,
                                             core._stream())
         _lib.check(rc, 'ddsp_stft_mag_backward_f32')
@@ -380,12 +415,31 @@ class SpectralLoss(Loss):
       _lib.check(lib.ddsp_loudness_from_mag_backward_f32(mags[1].data_ptr(), wt.data_ptr(), cot.data_ptr(), grad_mag.data_ptr(),
                                                          b, frames, bins, self.LOUDNESS_RANGE_DB, self.LOUDNESS_REF_DB,
                                                          core._stream()), 'ddsp_loudness_from_mag_backward_f32')
-      _lib.check(lib.ddsp_stft_frames_mag_backward_f32(audio.data_ptr(), grad_mag.data_ptr(), grad_audio.data_ptr(), b, n, n_fft,
-                                                       hop, n_fft // 2, frames, core._stream()),
-                 'ddsp_stft_frames_mag_backward_f32')
+      if self._slabs():
+        slabs = self._grad_ws.get(core.cached_workspace_bytes('ddsp_stft_frames_mag_backward_workspace_bytes', b, n, n_fft, hop,
+                                                              n_fft // 2, frames), dev)
+        _lib.check(lib.ddsp_stft_frames_mag_backward_det_f32(audio.data_ptr(), grad_mag.data_ptr(), grad_audio.data_ptr(),
+                                                             slabs.data_ptr(), slabs.numel(), b, n, n_fft, hop, n_fft // 2,
+                                                             frames, core._stream()),
+                   'ddsp_stft_frames_mag_backward_det_f32')
+      else:
+        _lib.check(lib.ddsp_stft_frames_mag_backward_f32(audio.data_ptr(), grad_mag.data_ptr(), grad_audio.data_ptr(), b, n, n_fft,
+                                                         hop, n_fft // 2, frames, core._stream()),
+                   'ddsp_stft_frames_mag_backward_f32')
 
   def _sizes(self):
     return (ctypes.c_int * len(self.fft_sizes))(*[int(v) for v in self.fft_sizes])
+
+  def _slab_workspace(self, audio):
+    b, n = audio.shape
+    sizes = tuple(int(v) for v in self.fft_sizes)
+    # (the size query takes a ctypes array: cached under the sizes themselves)
+    key = ('ddsp_spectral_loss_grad_workspace_bytes', b, n) + sizes
+    nbytes = core._ws_bytes_cache.get(key)
+    if nbytes is None:
+      nbytes = _lib.load().ddsp_spectral_loss_grad_workspace_bytes(b, n, self._sizes(), len(sizes))
+      core._ws_bytes_cache[key] = nbytes
+    return self._grad_ws.get(nbytes, audio.device)
 
   def _forward(self, target_audio, audio):
     b, n = audio.shape
@@ -414,6 +468,14 @@ class SpectralLoss(Loss):
     ws = self._ws.get(nbytes, audio.device)
     loss = torch.empty((), dtype=torch.float32, device=audio.device)
     grad_audio = torch.empty_like(audio)
+    if self._slabs():
+      slabs = self._slab_workspace(audio)
+      rc = lib.ddsp_spectral_loss_value_and_grad_det_f32(
+          target_audio.data_ptr(), audio.data_ptr(), loss.data_ptr(), grad_audio.data_ptr(), ws.data_ptr(),
+          ws.numel(), b, n, sizes, len(self.fft_sizes), float(self.mag_weight), float(self.logmag_weight),
+          slabs.data_ptr(), slabs.numel(), core._stream())
+      _lib.check(rc, 'ddsp_spectral_loss_value_and_grad_det_f32')
+      return loss, grad_audio
     rc = lib.ddsp_spectral_loss_value_and_grad_f32(
         target_audio.data_ptr(), audio.data_ptr(), loss.data_ptr(), grad_audio.data_ptr(), ws.data_ptr(),
         ws.numel(), b, n, sizes, len(self.fft_sizes), float(self.mag_weight), float(self.logmag_weight),
@@ -425,6 +487,14 @@ class SpectralLoss(Loss):
     b, n = audio.shape
     grad_loss = core.tf_float32(grad_loss).reshape(1).contiguous()
     grad_audio = torch.empty_like(audio)
+    if self._slabs():
+      slabs = self._slab_workspace(audio)
+      rc = _lib.load().ddsp_spectral_loss_backward_det_f32(
+          target_audio.data_ptr(), audio.data_ptr(), grad_loss.data_ptr(), grad_audio.data_ptr(), b, n,
+          self._sizes(), len(self.fft_sizes), float(self.mag_weight), float(self.logmag_weight),
+          slabs.data_ptr(), slabs.numel(), core._stream())
+      _lib.check(rc, 'ddsp_spectral_loss_backward_det_f32')
+      return grad_audio
     rc = _lib.load().ddsp_spectral_loss_backward_f32(
         target_audio.data_ptr(), audio.data_ptr(), grad_loss.data_ptr(), grad_audio.data_ptr(), b, n,
         self._sizes(), len(self.fft_sizes), float(self.mag_weight), float(self.logmag_weight),

@@ -343,6 +343,29 @@ int ddsp_spectral_loss_value_and_grad_f32(const float* target_audio, const float
                                           const int* fft_sizes, int n_sizes, float mag_weight,
                                           float logmag_weight, void* stream);
 
+/* The same gradient, bit-reproducible (opt-in): run to run, whatever else runs on the chip, and for a row whatever the other rows
+ * hold (a row's gradient depends on that row's data and on B alone).  No float atomics: every block stores its stretch of
+ * overlap-added samples to a slab of its own in grad_workspace, and a second, stream-ordered kernel writes each grad_audio[b][n]
+ * once, as the sum in this order:  g = 0;  for each entry of fft_sizes IN THE ORDER LISTED, g += (t = 0; t += the value of each
+ * block of that size that covers sample n, in ascending block index);  fp32 throughout.  (ddsp_stft_mag_backward_det_f32 and
+ * ddsp_stft_frames_mag_backward_det_f32 below add one scale in the same way: grad_audio[b][n] = grad_audio[b][n] + t - a loss
+ * built from them scale after scale, the loudness term last, follows the same contract.)
+ * grad_workspace: ddsp_spectral_loss_grad_workspace_bytes(...) bytes, 16-byte aligned = 4 B sum over sizes of (blocks per row x
+ * floats per block): a block takes G = max(1, 4096 / S) frames of hop F / 4 (S: the transform's size) and holds (G + 3) F / 4
+ * floats; transforms of 8192 points take one frame per block and hold F floats.  73 930 752 bytes at B = 32, N = 64 000 and the
+ * six default sizes.  0 where ddsp_spectral_loss_workspace_bytes returns 0.  A NULL grad_workspace is DDSP_ERR_NULL_POINTER, a
+ * short or misaligned one DDSP_ERR_WORKSPACE; the other arguments as in the two functions above. */
+size_t ddsp_spectral_loss_grad_workspace_bytes(int B, int N, const int* fft_sizes, int n_sizes);
+int ddsp_spectral_loss_backward_det_f32(const float* target_audio, const float* audio, const float* grad_loss,
+                                        float* grad_audio, int B, int N, const int* fft_sizes, int n_sizes,
+                                        float mag_weight, float logmag_weight, void* grad_workspace,
+                                        size_t grad_workspace_bytes, void* stream);
+int ddsp_spectral_loss_value_and_grad_det_f32(const float* target_audio, const float* audio, float* loss,
+                                              float* grad_audio, void* workspace, size_t workspace_bytes, int B, int N,
+                                              const int* fft_sizes, int n_sizes, float mag_weight,
+                                              float logmag_weight, void* grad_workspace, size_t grad_workspace_bytes,
+                                              void* stream);
+
 /* ---- the general form of losses.SpectralLoss (ddsp/losses.py:131-243): every term, loss_type and the weights mask ----
  * The 'L1' mag + logmag loss of the shipped configs is ddsp_spectral_loss_f32 above (spectra stay in LDS).  These three
  * entries serve the rest of the reference's argument space on spectrograms materialised in HBM, one FFT size at a time:
@@ -372,6 +395,13 @@ int ddsp_spectral_terms_f32(const float* target_mag, const float* value_mag, con
                             float cumsum_freq_weight, float logmag_weight, int first, void* stream);
 int ddsp_stft_mag_backward_f32(const float* audio, const float* grad_mag, float* grad_audio, int B, int N, int fft_size,
                                void* stream);
+/* ..._det: the same sum without float atomics (slabs in `workspace` + a gather; the order is stated at
+ * ddsp_spectral_loss_grad_workspace_bytes): grad_audio[b][n] = grad_audio[b][n] + (this scale's covering blocks, ascending), a
+ * plain read-modify-write.  workspace: ..._workspace_bytes(...) bytes (0: a size the call refuses), 16-byte aligned; NULL is
+ * DDSP_ERR_NULL_POINTER, short or misaligned DDSP_ERR_WORKSPACE. */
+size_t ddsp_stft_mag_backward_workspace_bytes(int B, int N, int fft_size);
+int ddsp_stft_mag_backward_det_f32(const float* audio, const float* grad_mag, float* grad_audio, void* workspace,
+                                   size_t workspace_bytes, int B, int N, int fft_size, void* stream);
 /* fft_size of the two calls above: a power of two in [16, 8192], or any other EVEN frame size in [34, 8190] (gin/models/vst/
  * vst_48k.gin:56 asks for 6144, 3072 .. 192; any since round 6) - tf.signal.stft then transforms the enclosing power of two S,
  * the frame zero-padded, every int(fft_size / 4) samples: bins = S / 2 + 1.
@@ -401,6 +431,12 @@ int ddsp_stft_frames_mag_ex_f32(const float* audio, float* mag, int B, int N, in
                                 int n_frames, void* stream);
 int ddsp_stft_frames_mag_backward_f32(const float* audio, const float* grad_mag, float* grad_audio, int B, int N, int fft_size,
                                       int hop, int pad_left, int n_frames, void* stream);
+/* ..._det: as ddsp_stft_mag_backward_det_f32, under the caller's frame geometry (a block of G = 8192 / fft_size frames holds
+ * (G - 1) hop + fft_size floats; the loudness geometry has up to nine covering blocks per sample). */
+size_t ddsp_stft_frames_mag_backward_workspace_bytes(int B, int N, int fft_size, int hop, int pad_left, int n_frames);
+int ddsp_stft_frames_mag_backward_det_f32(const float* audio, const float* grad_mag, float* grad_audio, void* workspace,
+                                          size_t workspace_bytes, int B, int N, int fft_size, int hop, int pad_left, int n_frames,
+                                          void* stream);
 /* spectral_ops.compute_mel / compute_logmel / compute_mfcc (ddsp/spectral_ops.py:73-133) under the frame geometry of
  * ddsp_stft_frames_mag_ex_f32, in one kernel: the magnitudes stay on chip, only out [B, n_frames, bins] (DDSP_MEL_LINEAR: the mel
  * spectrogram; DDSP_MEL_LOG: log(where(mel <= 0, eps, mel))) or [B, n_frames, mfcc_bins] (DDSP_MEL_MFCC: the first mfcc_bins
