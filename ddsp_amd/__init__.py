@@ -11,5 +11,6 @@ from ddsp_amd import losses
 from ddsp_amd import processors
 from ddsp_amd import synths
 from ddsp_amd import spectral_ops
+from ddsp_amd import training
 
 __version__ = '0.1.0'

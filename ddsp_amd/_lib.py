@@ -157,6 +157,9 @@ SIGNATURES = {
     'ddsp_hmm_log_prob_backward_f32': (c_int, [c_f32p] * 5 + [c_voidp, c_size_t, c_size_t, c_int, c_int] + [c_double] * 7 + [c_voidp]),
     'ddsp_hmm_viterbi_workspace_bytes': (c_size_t, [c_int] * 3),
     'ddsp_hmm_viterbi_f32': (c_int, [c_f32p] * 3 + [c_voidp, c_size_t, c_size_t, c_int, c_int] + [c_double] * 7 + [c_voidp]),
+    'ddsp_note_mask_f32': (c_int, [c_f32p] * 3 + [c_size_t] + [c_int] * 3 + [c_voidp]),
+    'ddsp_note_moments_f32': (c_int, [c_f32p] * 7 + [c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_note_spread_f32': (c_int, [c_f32p] * 7 + [c_size_t] + [c_int] * 3 + [c_voidp]),
     'ddsp_fft_convolve_grad_audio_f32': (c_int, [c_f32p] * 3 + [c_int] * 7 + [c_voidp]),
     'ddsp_fft_convolve_grad_ir_f32': (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_voidp]),
     'ddsp_sinc_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_float, c_voidp]),
@@ -204,6 +207,8 @@ CONSISTENCY_MAX_K = 1024                # sinusoids / harmonics a frame's block 
 CONSISTENCY_MAX_POINTS = 256
 CONSISTENCY_MAX_GAUSSIANS = 4096
 HMM_MAX_PITCHES = 1024                  # states of HmmTranscriber a block holds in registers (csrc/hmm.hip)
+NOTES_SUM = 0x1
+NOTES_MAX_REGIONS = 1024                # regions whose note-on flags get_note_mask's block keeps in LDS (csrc/notes.hip)
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
 CONV_ADD_DRY = 0x1

@@ -230,6 +230,18 @@ def safe_log(x, eps=1e-5):
   return out
 
 
+def diff(x, axis=-1):
+  """core.diff (ddsp/core.py:171-199): the finite difference along an axis, one element shorter there.
+
+  Two slices and a subtraction in torch (differentiable); the reference's ValueError for an axis out of range."""
+  x = tf_float32(x)
+  ndim = x.dim()
+  if axis >= ndim or axis < -ndim:
+    raise ValueError('Invalid axis index: %d for tensor with only %d axes.' % (axis, ndim))
+  lead = (slice(None),) * (axis % ndim)
+  return x[lead + (slice(1, None),)] - x[lead + (slice(None, -1),)]
+
+
 def get_harmonic_frequencies(frequencies, n_harmonics):
   """core.get_harmonic_frequencies (ddsp/core.py:1028-1045): [batch, :, 1] fundamentals -> [batch, :, n_harmonics]."""
   frequencies = tf_float32(frequencies).contiguous()

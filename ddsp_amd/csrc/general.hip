@@ -1118,6 +1118,13 @@ DDSP_WEAK int ddsp_hmm_log_prob_backward_f32(const float*, const float*, const f
 DDSP_WEAK size_t ddsp_hmm_viterbi_workspace_bytes(int, int, int) { return 0; }
 DDSP_WEAK int ddsp_hmm_viterbi_f32(const float*, const float*, int*, void*, size_t, size_t, int, int, double, double, double, double,
                                    double, double, double, void*) { return DDSP_ERR_UNSUPPORTED; }
+// and of csrc/notes.hip
+DDSP_WEAK int ddsp_note_mask_f32(const float*, const float*, float*, size_t, int, int, int, void*) { return DDSP_ERR_UNSUPPORTED; }
+DDSP_WEAK int ddsp_note_moments_f32(const float*, const float*, float*, float*, float*, float*, float*, size_t, int, int, int, int, void*) {
+  return DDSP_ERR_UNSUPPORTED;
+}
+DDSP_WEAK int ddsp_note_spread_f32(const float*, const float*, const float*, const float*, const float*, const float*, float*, size_t, int,
+                                   int, int, void*) { return DDSP_ERR_UNSUPPORTED; }
 // and of csrc/fir_grad.hip
 DDSP_WEAK int ddsp_fft_convolve_grad_audio_f32(const float*, const float*, float*, int, int, int, int, int, int, int, void*) {
   return DDSP_ERR_UNSUPPORTED;

@@ -925,6 +925,38 @@ int ddsp_hmm_viterbi_f32(const float* pitch, const float* amps, int* states, voi
                          void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The note pooling of ddsp/training/nn.py:375-557: csrc/notes.hip.  mask is [rows, steps, notes], x [rows, steps, dims],
+ * per-note tensors [rows, notes, dims].  Nothing of size rows * steps * notes * dims exists, and nothing of size
+ * rows * steps * notes but the mask; the cost of the moments and of the spread follows the mask's non-zero entries.  Every
+ * formula holds for any fp32 mask (weights m in the mean, m^2 in the variance).  No workspace, no atomics, fixed summation
+ * orders: the same bits on every run and for any subset of the rows.
+ *
+ * ddsp_note_mask_f32: pitch [rows, steps] (and onset [rows, steps], or NULL) -> mask of 0.0 / 1.0, every element written.
+ *   onset == NULL: get_note_mask (:375-425) - step 0 starts region 0, step p in 1 .. steps - 2 starts a region when
+ *   pitch[p] != pitch[p - 1], THE LAST STEP NEVER DOES; note_on_only keeps the regions whose pitch sum (hence mean) is > 0.
+ *   onset != NULL: get_note_mask_from_onset (:428-476) - step p >= 1 advances the region index by (int)onset[p];
+ *   note_on_only keeps the steps with pitch > 0.  Steps whose region index is outside [0, max_regions) get a zero row.
+ * ddsp_note_moments_f32: get_note_moments (:484-520).  Per (row, note), in ascending time and fp64: length = sum m (0 -> 1e-7,
+ *   core.safe_divide), mean = sum m x / length, then a second pass for std = sqrt(sum (m (x - mean))^2 / length) and
+ *   s2 = sum m^2 (x - mean) (what the backward needs).  mean_lo = mean - (float)mean, what the fp32 result lost of the fp64
+ *   mean (the backward's x - mean cancels on notes of nearly equal values).  std, s2, mean_lo and lengths ([rows, notes], the
+ *   safe length) may each be NULL (s2 needs std).  flags & DDSP_NOTES_SUM: `mean` receives sum m x without the division (the adjoint of the spread
+ *   in its values); std, s2, mean_lo and lengths must be NULL.
+ * ddsp_note_spread_f32: out[r, t, :] = sum_n m (a[r, n, :] + c[r, n, :] m (x[r, t, :] - mean[r, n, :] - mean_lo[r, n, :])); c may be
+ *   NULL (then x, mean and mean_lo are not read), and mean_lo may be NULL where c is given.  c == NULL is the forward of pool_over_notes (:523-547) and, with dims = 1, of
+ *   get_short_note_loss_mask (:550-557); with c it is the backward of the moments in x.
+ * Bounds (DDSP_ERR_UNSUPPORTED beyond): max_regions <= 1024 in ddsp_note_mask_f32; rows * notes and rows * steps below 2^31;
+ * dims <= 256 * 65535.  steps >= 2 for the mask (DDSP_ERR_BAD_SHAPE).
+ */
+#define DDSP_NOTES_SUM 0x1
+int ddsp_note_mask_f32(const float* pitch, const float* onset, float* mask, size_t rows, int steps, int max_regions,
+                       int note_on_only, void* stream);
+int ddsp_note_moments_f32(const float* x, const float* mask, float* mean, float* std, float* s2, float* mean_lo, float* lengths,
+                          size_t rows, int steps, int notes, int dims, int flags, void* stream);
+int ddsp_note_spread_f32(const float* mask, const float* a, const float* c, const float* x, const float* mean, const float* mean_lo,
+                         float* out, size_t rows, int steps, int notes, int dims, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
