@@ -168,6 +168,12 @@ SIGNATURES = {
     'ddsp_sinc_impulse_response_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_int, c_voidp]),
     'ddsp_frequency_impulse_response_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_int, c_voidp]),
     'ddsp_exp_sigmoid_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t] + [c_float] * 3 + [c_voidp]),
+    'ddsp_critical_bands_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_int] + [c_f32p] * 3 + [c_float] * 3 + [c_voidp]),
+    'ddsp_critical_bands_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_int] + [c_f32p] * 3 + [c_float] * 3 + [c_voidp]),
+    'ddsp_harmonic_wavetable_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_harmonic_wavetable_backward_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_scale_convert_f32': (c_int, [c_f32p] * 2 + [c_size_t, c_int, c_float, c_float, c_voidp]),
+    'ddsp_scale_convert_backward_f32': (c_int, [c_f32p] * 3 + [c_size_t, c_int, c_float, c_float, c_voidp]),
     'ddsp_profile_kernel_count': (c_int, []),
     'ddsp_profile_kernel_name': (ctypes.c_char_p, [c_int]),
     'ddsp_profile_begin': (c_int, [c_uint, c_int]),
@@ -198,6 +204,9 @@ SIN_AMP_LINEAR = 0x10
 SIN_MAX_SIGMOID_DEPTH = 64
 CONVERT_OPS = {'midi_to_hz': 0, 'midi_to_hz_zero_silence': 1, 'hz_to_midi': 2, 'unit_to_midi': 3, 'unit_to_midi_clip': 4,
                'midi_to_unit': 5, 'midi_to_unit_clip': 6, 'logb': 7, 'log_floor': 8}
+SCALE_OPS = {'hz_to_bark': 0, 'bark_to_hz': 1, 'hz_to_mel': 2, 'mel_to_hz': 3, 'hz_to_erb': 4, 'soft_limit': 5, 'log_scale': 6,
+             'sym_exp_sigmoid': 7, 'nan_to_num': 8}
+HARMONIC_WAVETABLE_SIZES = (64, 8192)   # powers of two the fused kernel of csrc/harmonic_wavetable.hip transforms
 DB_OPS = {'power_to_db': 0, 'amplitude_to_db': 1, 'db_to_power': 2, 'db_to_amplitude': 3}
 MEL_MODES = {'mel': 0, 'logmel': 1, 'mfcc': 2}
 ENERGY_DB = 0x1

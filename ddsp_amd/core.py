@@ -1666,3 +1666,319 @@ def _row_mean(x):
   if _needs_grad(x):
     return _RowMeanFunction.apply(x)
   return _RowMeanFunction.forward(_NoCtx(), x)
+
+
+# --------------------------------------------------------------------------------------
+# the rest of ddsp/core.py: psychoacoustic scales, soft_limit / log_scale / sym_exp_sigmoid, critical bands, harmonic
+# wavetables (csrc/scale_fns.hip, critical_bands.hip, harmonic_wavetable.hip) and host plumbing
+# --------------------------------------------------------------------------------------
+class _ScaleFunction(torch.autograd.Function):
+  """ddsp_scale_convert_f32 with its adjoint (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, x, op, p0, p1):
+    ctx.save_for_backward(x)
+    ctx.args = (_lib.SCALE_OPS[op], float(p0), float(p1))
+    out = torch.empty_like(x)
+    if x.numel():
+      rc = _lib.load().ddsp_scale_convert_f32(x.data_ptr(), out.data_ptr(), x.numel(), *ctx.args, _stream())
+      _lib.check(rc, 'ddsp_scale_convert_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    x, = ctx.saved_tensors
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty_like(x)
+    if x.numel():
+      rc = _lib.load().ddsp_scale_convert_backward_f32(x.data_ptr(), grad_out.data_ptr(), grad.data_ptr(), x.numel(), *ctx.args,
+                                                       _stream())
+      _lib.check(rc, 'ddsp_scale_convert_backward_f32')
+    return grad, None, None, None
+
+
+def _scale(op, x, p0=0.0, p1=0.0):
+  x = tf_float32(x)
+  if _needs_grad(x):
+    return _ScaleFunction.apply(x, op, p0, p1)
+  return _ScaleFunction.forward(_NoCtx(), x, op, p0, p1)
+
+
+def hz_to_bark(hz):
+  """core.hz_to_bark (ddsp/core.py:351-353): 26.81 / (1 + 1960 / hz) - 0.53 (Traunmuller 1990); hz_to_bark(0) = -0.53."""
+  return _scale('hz_to_bark', hz)
+
+
+def bark_to_hz(bark):
+  """core.bark_to_hz (ddsp/core.py:356-358): 1960 / (26.81 / (bark + 0.53) - 1); bark_to_hz(-0.53) = 0."""
+  return _scale('bark_to_hz', bark)
+
+
+def hz_to_mel(hz):
+  """core.hz_to_mel (ddsp/core.py:361-363): 2595 logb(1 + hz / 700, 10), with logb's safe logarithm."""
+  return _scale('hz_to_mel', hz)
+
+
+def mel_to_hz(mel):
+  """core.mel_to_hz (ddsp/core.py:366-368): 700 (10^(mel / 2595) - 1)."""
+  return _scale('mel_to_hz', mel)
+
+
+def hz_to_erb(hz):
+  """core.hz_to_erb (ddsp/core.py:371-382): equivalent rectangular bandwidths, 0.108 hz + 24.7 (Moore & Glasberg 1996)."""
+  return _scale('hz_to_erb', hz)
+
+
+def soft_limit(x, x_min=0.0, x_max=1.0):
+  """core.soft_limit (ddsp/core.py:236-238): softplus(x) + x_min - softplus(x - (x_max - x_min)).  As in the reference a
+  value well inside the range comes out as x + x_min."""
+  return _scale('soft_limit', x, x_min, x_max)
+
+
+def log_scale(x, min_x, max_x):
+  """core.log_scale (ddsp/core.py:229-233): [-1, 1] logarithmically to [min_x, max_x] (the bounds are positive numbers)."""
+  if not (float(min_x) > 0.0 and float(max_x) > 0.0):
+    raise ValueError('log_scale needs positive bounds, got min_x={} and max_x={}'.format(min_x, max_x))
+  return _scale('log_scale', x, min_x, max_x)
+
+
+def sym_exp_sigmoid(x, width=8.0):
+  """core.sym_exp_sigmoid (ddsp/core.py:407-411): exp_sigmoid(width (|x| / 2 - 1)); the gradient at x = 0 is 0, as tf.abs has it."""
+  return _scale('sym_exp_sigmoid', x, width)
+
+
+def nan_to_num(x, value=0.0):
+  """core.nan_to_num (ddsp/core.py:202-204): NaNs replaced by `value`; the gradient passes where x is not NaN."""
+  return _scale('nan_to_num', x, value)
+
+
+def log10(x, eps=1e-5):
+  """core.log10 (ddsp/core.py:224-226): logb(x, 10, eps).  Forward only, like logb."""
+  return logb(x, base=10.0, eps=eps)
+
+
+class _GradientReversalFunction(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, x):
+    return x.view_as(x)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    return -grad_out
+
+
+def gradient_reversal(x):
+  """core.gradient_reversal (ddsp/core.py:241-243): the identity forward, the gradient negated."""
+  x = tf_float32(x)
+  return _GradientReversalFunction.apply(x) if _needs_grad(x) else x
+
+
+# ---- frequencies_critical_bands  (ddsp/core.py:510-569) ----
+def _np_hz_to_bark(hz):
+  return 26.81 / (1.0 + (1960.0 / hz)) - 0.53
+
+
+def _np_bark_to_hz(bark):
+  return 1960.0 / (26.81 / (bark + 0.53) - 1.0)
+
+
+def _np_hz_to_mel(hz):
+  return 2595.0 * (np.log(np.where(1.0 + hz / 700.0 <= 0.0, 1e-5, 1.0 + hz / 700.0)) / np.log(10.0))
+
+
+def _np_mel_to_hz(mel):
+  return 700.0 * (10.0**(mel / 2595.0) - 1.0)
+
+
+def critical_band_tables(n_sinusoids, depth=1, depth_scale=10.0, hz_min=20.0, hz_max=8000.0, scale='bark'):
+  """The constants of frequencies_critical_bands as float32 arrays: (f_center [n_sinusoids], bandwidths [n_sinusoids],
+  depth_modifier [depth]).  The centres lie evenly on the bark scale (scale == 'bark') or the mel scale (any other string,
+  as in the reference) between hz_min and hz_max, the bandwidths are their ERBs; both are made in float64 and rounded once.
+  depth_modifier = depth_scale^-d in float32, as tf.range(depth, dtype=float32) makes it."""
+  with np.errstate(divide='ignore', over='ignore', under='ignore'):
+    if scale == 'bark':
+      grid = np.linspace(_np_hz_to_bark(np.float64(hz_min)), _np_hz_to_bark(np.float64(hz_max)), int(n_sinusoids))
+      f_center = _np_bark_to_hz(grid)
+    else:
+      grid = np.linspace(_np_hz_to_mel(np.float64(hz_min)), _np_hz_to_mel(np.float64(hz_max)), int(n_sinusoids))
+      f_center = _np_mel_to_hz(grid)
+    bandwidths = 0.108 * f_center + 24.7
+    depth_modifier = np.power(np.float32(depth_scale), -np.arange(int(depth), dtype=np.float32)).astype(np.float32)
+  return f_center.astype(np.float32), bandwidths.astype(np.float32), depth_modifier
+
+
+_critical_band_cache = {}
+
+
+def _critical_band_device_tables(key, device):
+  """critical_band_tables(*key) on `device`, made once per argument tuple and device."""
+  ck = key + (str(device),)
+  tables = _critical_band_cache.get(ck)
+  if tables is None:
+    tables = tuple(torch.as_tensor(t, device=device).contiguous() for t in critical_band_tables(*key))
+    _critical_band_cache[ck] = tables
+  return tables
+
+
+class _CriticalBandsFunction(torch.autograd.Function):
+  """torch.autograd node of core.frequencies_critical_bands (plumbing: both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, freqs, tables, k, depth, bandwidth_scale, hz_min, hz_max):
+    ctx.save_for_backward(freqs)
+    ctx.args = (k, depth) + tuple(t.data_ptr() for t in tables) + (bandwidth_scale, hz_min, hz_max)
+    ctx.tables = tables
+    b, t, _ = freqs.shape
+    out = torch.empty((b, t, k), dtype=torch.float32, device=freqs.device)
+    if out.numel():
+      rc = _lib.load().ddsp_critical_bands_f32(freqs.data_ptr(), out.data_ptr(), b * t, *ctx.args, _stream())
+      _lib.check(rc, 'ddsp_critical_bands_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    freqs, = ctx.saved_tensors
+    b, t, _ = freqs.shape
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty_like(freqs)
+    if grad.numel():
+      rc = _lib.load().ddsp_critical_bands_backward_f32(freqs.data_ptr(), grad_out.data_ptr(), grad.data_ptr(), b * t, *ctx.args,
+                                                        _stream())
+      _lib.check(rc, 'ddsp_critical_bands_backward_f32')
+    return grad, None, None, None, None, None, None
+
+
+def frequencies_critical_bands(freqs, depth=1, depth_scale=10.0, bandwidth_scale=1.0, hz_min=20.0, hz_max=8000.0, scale='bark'):
+  """core.frequencies_critical_bands (ddsp/core.py:510-569): centre frequencies evenly spaced on the bark (scale='bark') or mel
+  (any other string) scale between hz_min and hz_max, each moved within bandwidth_scale ERBs of its centre by
+  sum_d tanh(freqs[..., d]) depth_scale^-d and passed through soft_limit(hz_min, hz_max).  freqs [batch, time,
+  n_sinusoids * depth] or [batch, time, n_sinusoids, depth] -> [batch, time, n_sinusoids].  One kernel per direction with
+  coalesced loads at every depth (csrc/critical_bands.hip); differentiable; any depth >= 1."""
+  raw = tf_float32(freqs)
+  flat, k, depth = _depth_layout(raw, depth)
+  tables = _critical_band_device_tables((k, depth, float(depth_scale), float(hz_min), float(hz_max), 'bark' if scale == 'bark' else 'mel'),
+                                        flat.device)
+  args = (flat, tables, k, depth, float(bandwidth_scale), float(hz_min), float(hz_max))
+  if _needs_grad(raw):
+    return _CriticalBandsFunction.apply(*args)
+  return _CriticalBandsFunction.forward(_NoCtx(), *args)
+
+
+# ---- harmonic_distribution_to_wavetable  (ddsp/core.py:1217-1235) ----
+def harmonic_wavetable_length(n_harmonics, n_wavetable):
+  """Points of the table harmonic_distribution_to_wavetable returns: 2 (n_harmonics + int(n_wavetable / 2 - n_harmonics)),
+  which is n_wavetable when that is even and n_wavetable - 1 when it is odd.  ValueError where the reference's tf.pad
+  fails on a negative padding (more harmonics than n_wavetable / 2)."""
+  n_pad = int(n_wavetable / 2 - n_harmonics)
+  if n_harmonics < 1 or n_pad < 0 or n_wavetable / 2 - n_harmonics < 0:
+    raise ValueError('harmonic_distribution_to_wavetable: {} harmonics do not fit a wavetable of {} points (at most '
+                     'n_wavetable / 2)'.format(n_harmonics, n_wavetable))
+  return 2 * (int(n_harmonics) + n_pad)
+
+
+def _harmonic_wavetable_fused(length):
+  lo, hi = _lib.HARMONIC_WAVETABLE_SIZES
+  return lo <= length <= hi and length & (length - 1) == 0
+
+
+class _HarmonicWavetableFunction(torch.autograd.Function):
+  """torch.autograd node of core.harmonic_distribution_to_wavetable on the fused kernel (both directions are C-ABI calls)."""
+
+  @staticmethod
+  def forward(ctx, hd, length, scale):
+    ctx.args = (int(hd.shape[-1]), length, scale)
+    rows = hd.numel() // hd.shape[-1]
+    out = torch.empty(tuple(hd.shape[:-1]) + (length,), dtype=torch.float32, device=hd.device)
+    if rows:
+      rc = _lib.load().ddsp_harmonic_wavetable_f32(hd.data_ptr(), out.data_ptr(), rows, *ctx.args, _stream())
+      _lib.check(rc, 'ddsp_harmonic_wavetable_f32')
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    k, length, scale = ctx.args
+    grad_out = tf_float32(grad_out)
+    grad = torch.empty(tuple(grad_out.shape[:-1]) + (k,), dtype=torch.float32, device=grad_out.device)
+    if grad.numel():
+      rc = _lib.load().ddsp_harmonic_wavetable_backward_f32(grad_out.data_ptr(), grad.data_ptr(), grad.numel() // k, k, length, scale,
+                                                            _stream())
+      _lib.check(rc, 'ddsp_harmonic_wavetable_backward_f32')
+    return grad, None, None
+
+
+def harmonic_distribution_to_wavetable(harmonic_distribution, n_wavetable=2048):
+  """core.harmonic_distribution_to_wavetable (ddsp/core.py:1217-1235): [batch, time, n_harmonics] -> wavetables
+  [batch, time, L] for core.wavetable_synthesis / synths.Wavetable, L = harmonic_wavetable_length(n_harmonics, n_wavetable):
+  table[n] = (n_wavetable / L) sum_k w_k hd[k - 1] cos(2 pi k n / L), the reference's pad -> irfft -> scale.
+
+  L a power of two from 64 to 8192 runs one fused kernel per direction (csrc/harmonic_wavetable.hip); any other length -
+  an odd n_wavetable gives L = n_wavetable - 1 - takes the reference's own chain with torch.fft.irfft.  Differentiable."""
+  hd = tf_float32(harmonic_distribution)
+  if hd.dim() < 1:
+    raise ValueError('harmonic_distribution must be [..., n_harmonics], got a scalar')
+  k = int(hd.shape[-1])
+  length = harmonic_wavetable_length(k, n_wavetable)
+  if not _harmonic_wavetable_fused(length):
+    fft_in = torch.nn.functional.pad(hd, (1, length // 2 - k))
+    return torch.fft.irfft(torch.complex(fft_in, torch.zeros_like(fft_in)), n=length) * (n_wavetable / 2)
+  scale = float(n_wavetable) / float(length)
+  if _needs_grad(hd):
+    return _HarmonicWavetableFunction.apply(hd, length, scale)
+  return _HarmonicWavetableFunction.forward(_NoCtx(), hd, length, scale)
+
+
+# ---- host plumbing  (ddsp/core.py:64-75, 132-168, 717-729) ----
+def copy_if_tf_function(x):
+  """core.copy_if_tf_function (ddsp/core.py:64-75): the reference copies inside a tf.function; there is none here."""
+  return x
+
+
+def leaf_key(nested_key, delimiter='/'):
+  """Returns the leaf node key name of "key/key/key" (ddsp/core.py:132-145)."""
+  return nested_key.split(delimiter)[-1]
+
+
+def map_shape(x):
+  """Recursively infer tensor shapes for a (nested) dictionary of tensors, as lists of ints (ddsp/core.py:148-150)."""
+  if isinstance(x, dict):
+    return {k: map_shape(v) for k, v in x.items()}
+  if isinstance(x, (list, tuple)):
+    return type(x)(map_shape(v) for v in x)
+  return [int(d) for d in np.shape(x)] if not isinstance(x, torch.Tensor) else [int(d) for d in x.shape]
+
+
+def pad_axis(x, padding=(0, 0), axis=0, **pad_kwargs):
+  """core.pad_axis (ddsp/core.py:153-168): pads one axis of a tensor by (before, after).  pad_kwargs are tf.pad's `mode`
+  ('CONSTANT', 'REFLECT', 'SYMMETRIC') and `constant_values`, as spectral_ops.pad takes them.  Host plumbing (torch)."""
+  x = tf_float32(x)
+  mode = str(pad_kwargs.pop('mode', 'CONSTANT')).upper()
+  constant_values = pad_kwargs.pop('constant_values', 0)
+  if pad_kwargs:
+    raise TypeError('pad_axis got unexpected keyword arguments {}'.format(sorted(pad_kwargs)))
+  before, after = (int(p) for p in padding)
+  if before < 0 or after < 0:
+    raise ValueError('Paddings must be non-negative, got {}'.format(tuple(padding)))
+  if x.dim() == 0 or not -x.dim() <= axis < x.dim():
+    raise ValueError('Invalid axis index: %d for tensor with only %d axes.' % (axis, x.dim()))
+  n = int(x.shape[axis])
+  x = x.movedim(axis, -1)
+  if mode == 'CONSTANT':
+    out = torch.nn.functional.pad(x, (before, after), value=float(constant_values))
+  elif mode in ('REFLECT', 'SYMMETRIC'):
+    skip = 1 if mode == 'REFLECT' else 0
+    if max(before, after) + skip > n:
+      raise ValueError('{} padding of {} needs at least {} samples, got {}'.format(mode, max(before, after),
+                                                                                 max(before, after) + skip, n))
+    left = x[..., skip:skip + before].flip(-1)
+    right = x[..., n - skip - after:n - skip].flip(-1)
+    out = torch.cat([left, x, right], dim=-1)
+  else:
+    raise ValueError('`mode` must be one of CONSTANT, REFLECT, SYMMETRIC, received ({}).'.format(mode))
+  return out.movedim(-1, axis).contiguous()
+
+
+def center_crop(audio, frame_size):
+  """core.center_crop (ddsp/core.py:717-729): removes the padding of centred frames, audio[:, p:-p] with p = frame_size // 2
+  (python slice semantics included: p = 0 leaves nothing, as in the reference)."""
+  pad_amount = int(frame_size // 2)
+  return audio[:, pad_amount:-pad_amount]

@@ -12,7 +12,9 @@ fp64 from TensorFlow's published source (tf.signal.linear_to_mel_weight_matrix, 
 DESIGN.md section 2) and cached per argument tuple.  Beyond the kernel's limits (more mel bins than the transform has points,
 more MFCCs than mel bins) the same functions run as compute_mag followed by the table products with torch.
 
-Not offered: compute_f0 / PretrainedCREPE (a pretrained network) and pad_or_trim_to_expected_length."""
+pad_or_trim_to_expected_length (:367-423) is host plumbing: numpy in, numpy out; tensor in, tensor out.
+
+Not offered: compute_f0 / PretrainedCREPE (a pretrained network)."""
 import numpy as np
 import torch
 
@@ -395,3 +397,29 @@ def compute_power(audio, sample_rate=16000, frame_rate=250, frame_size=512, ref_
   """Power in dB [batch, n_frames] (spectral_ops.py:237-249): core.amplitude_to_db(compute_rms_energy(...), ref_db, range_db),
   in the energy kernel (the same bits as the two calls)."""
   return _frame_energy(audio, sample_rate, frame_rate, frame_size, padding, True, ref_db, range_db)
+
+
+def pad_or_trim_to_expected_length(vector, expected_len, pad_value=0, len_tolerance=20, use_tf=False):
+  """Make the last axis of a 1-D or 2-D vector `expected_len` long (spectral_ops.py:367-423): padded at the end with
+  pad_value or trimmed; ValueError when the lengths differ by more than len_tolerance to begin with.  A numpy array comes
+  back as a numpy array, a tensor as a tensor (differentiable); `use_tf` is accepted and has nothing to choose."""
+  del use_tf
+  expected_len = int(expected_len)
+  vector_len = int(vector.shape[-1])
+  if abs(vector_len - expected_len) > len_tolerance:
+    raise ValueError('Vector length: {} differs from expected length: {} '
+                     'beyond tolerance of : {}'.format(vector_len, expected_len, len_tolerance))
+  is_tensor = isinstance(vector, torch.Tensor)
+  if not is_tensor:
+    vector = np.asarray(vector)
+  is_1d = len(vector.shape) == 1
+  vector = vector[None, :] if is_1d else vector
+  if vector_len < expected_len:
+    n_padding = expected_len - vector_len
+    if is_tensor:
+      vector = torch.nn.functional.pad(vector, (0, n_padding), value=float(pad_value))
+    else:
+      vector = np.pad(vector, ((0, 0), (0, n_padding)), mode='constant', constant_values=pad_value)
+  elif vector_len > expected_len:
+    vector = vector[..., :expected_len]
+  return vector[0] if is_1d else vector

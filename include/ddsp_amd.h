@@ -957,6 +957,57 @@ int ddsp_note_spread_f32(const float* mask, const float* a, const float* c, cons
                          float* out, size_t rows, int steps, int notes, int dims, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The rest of ddsp/core.py: csrc/critical_bands.hip, csrc/harmonic_wavetable.hip, csrc/scale_fns.hip.  No workspace, no
+ * atomics, fixed summation orders: the same bits on every run and for a row alone or in a batch.
+ *
+ * ddsp_critical_bands_f32: core.frequencies_critical_bands (:510-569) on `rows` = B * T frames.  freqs [rows, K * depth]
+ *   (a sinusoid's `depth` values side by side) -> out [rows, K]:
+ *     out = soft_limit(f_center[k] + bandwidth_scale * bandwidths[k] * sum_d tanh(freqs[k, d]) * depth_modifier[d], hz_min, hz_max)
+ *   with soft_limit(x, lo, hi) = softplus(x) + lo - softplus(x - (hi - lo)).  f_center, bandwidths [K] and depth_modifier
+ *   [depth] are device tables of the caller (the host layer: the bark / mel grid, its ERBs, depth_scale^-d).  The loads
+ *   are coalesced for every depth; the sum over d runs in ascending d in one thread.
+ * ddsp_critical_bands_backward_f32: grad_out [rows, K] -> grad_freqs [rows, K * depth]; recomputes the forward's sum, so
+ *   nothing but freqs is saved.
+ *   K, depth >= 1 (else DDSP_ERR_BAD_SHAPE); rows * K below 2^31 (else DDSP_ERR_UNSUPPORTED).
+ *
+ * ddsp_harmonic_wavetable_f32: core.harmonic_distribution_to_wavetable (:1217-1235).  hd [rows, K] -> out [rows, L]:
+ *     out[r, n] = scale * sum_{k = 1 .. K} w_k hd[r, k - 1] cos(2 pi k n / L),   w_k = 1, but w_{L/2} = 1/2
+ *   (the irfft of the distribution padded to L / 2 + 1 bins; the reference's scale is n_wavetable / L), one fused kernel on
+ *   the LDS transforms of the STFT kernels.  ddsp_harmonic_wavetable_backward_f32: grad_out [rows, L] -> grad_hd [rows, K].
+ *   L even and K <= L / 2 (else DDSP_ERR_BAD_SHAPE); L a power of two in [64, 8192] (else DDSP_ERR_UNSUPPORTED: the host
+ *   layer takes other lengths through its general path).
+ *
+ * ddsp_scale_convert_f32 / ddsp_scale_convert_backward_f32 (grad_in = grad_out * d op(in) / d in) on n values:
+ *   HZ_TO_BARK 26.81 / (1 + 1960 / x) - 0.53 and BARK_TO_HZ 1960 / (26.81 / (x + 0.53) - 1), IEEE results at the poles
+ *   (hz_to_bark(0) = -0.53, bark_to_hz(-0.53) = 0); HZ_TO_MEL 2595 log10(1 + x / 700) with core.logb's safe log;
+ *   MEL_TO_HZ 700 (10^(x / 2595) - 1); HZ_TO_ERB 0.108 x + 24.7; SOFT_LIMIT with p0 = x_min, p1 = x_max; LOG_SCALE
+ *   exp((1 - u) ln p0 + u ln p1), u = (x + 1) / 2, p0 = min_x, p1 = max_x; SYM_EXP_SIGMOID exp_sigmoid(p0 (|x| / 2 - 1)),
+ *   p0 = width, slope 0 at x = 0; NAN_TO_NUM p0 where x is NaN (no gradient there), x elsewhere.
+ *   An unknown op is DDSP_ERR_BAD_SHAPE.
+ */
+#define DDSP_SCALE_HZ_TO_BARK 0
+#define DDSP_SCALE_BARK_TO_HZ 1
+#define DDSP_SCALE_HZ_TO_MEL 2
+#define DDSP_SCALE_MEL_TO_HZ 3
+#define DDSP_SCALE_HZ_TO_ERB 4
+#define DDSP_SCALE_SOFT_LIMIT 5
+#define DDSP_SCALE_LOG_SCALE 6
+#define DDSP_SCALE_SYM_EXP_SIGMOID 7
+#define DDSP_SCALE_NAN_TO_NUM 8
+int ddsp_critical_bands_f32(const float* freqs, float* out, size_t rows, int K, int depth, const float* f_center,
+                            const float* bandwidths, const float* depth_modifier, float bandwidth_scale, float hz_min,
+                            float hz_max, void* stream);
+int ddsp_critical_bands_backward_f32(const float* freqs, const float* grad_out, float* grad_freqs, size_t rows, int K,
+                                     int depth, const float* f_center, const float* bandwidths, const float* depth_modifier,
+                                     float bandwidth_scale, float hz_min, float hz_max, void* stream);
+int ddsp_harmonic_wavetable_f32(const float* hd, float* out, size_t rows, int K, int L, float scale, void* stream);
+int ddsp_harmonic_wavetable_backward_f32(const float* grad_out, float* grad_hd, size_t rows, int K, int L, float scale,
+                                         void* stream);
+int ddsp_scale_convert_f32(const float* in, float* out, size_t n, int op, float p0, float p1, void* stream);
+int ddsp_scale_convert_backward_f32(const float* in, const float* grad_out, float* grad_in, size_t n, int op, float p0,
+                                    float p1, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Tracing (the reference has none beyond wall-clock logs): opt-in
  * HIP-event brackets around individual kernels, recorded on the stream they are launched
  * on.  ddsp_profile_begin(mask, max_records) turns it on for the kernels whose bit is set
