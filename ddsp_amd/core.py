@@ -38,6 +38,15 @@ def tf_float32(x):
   return torch.as_tensor(np.asarray(x, dtype=np.float32), device=_device()).contiguous()
 
 
+def aligned16(x):
+  """`x` (contiguous fp32) itself when it starts on a 16-byte boundary, else a copy in an allocation of its own, which does.
+  A contiguous view (`flat[a:b].view(...)`, `batch[r:r + 1]`, a chunk of a gradient bucket) starts on any 4-byte boundary.
+  For the pointers by whose alignment a C entry picks its kernel (the supplied noise of ddsp_filtered_noise_f32, the audio and the
+  impulse response of ddsp_fft_convolve_same_f32 / ddsp_fft_convolve_f32) and for ddsp_add_f32, which takes no other: the result
+  then never depends on the address.  The copy runs only for such views; an allocation of torch's is aligned to 256 bytes or more."""
+  return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+
+
 def _check_current_device(x):
   """Every kernel is enqueued on the CURRENT device's current stream (one process per GPU is the model): a tensor
   that lives on another GPU of the process would be handed to a stream of the wrong device.  Fail loudly."""
@@ -557,6 +566,7 @@ def harmonic_synthesis(frequencies, amplitudes, harmonic_shifts=None,
     return audio
   nbytes = lib.ddsp_harmonic_workspace_bytes(b, f, k, int(n_samples))
   ws = (workspace or _default_ws).get(nbytes, amplitudes.device)
+  harmonic_distribution = aligned16(harmonic_distribution)     # (the entry picks its kernel by this address)
   rc = lib.ddsp_harmonic_signal_f32(
       amplitudes.data_ptr(), harmonic_distribution.data_ptr(), frequencies.data_ptr(),
       audio.data_ptr(), ws.data_ptr(), ws.numel(), b, f, k, int(n_samples), int(sample_rate),
@@ -849,6 +859,7 @@ def _fft_convolve_run(audio, impulse_response, crop):
   """fft_convolve on checked arguments: audio [B, N], impulse_response [B or 1, F, L], crop = (start as requested, first kept
   index, number of kept samples, delay_compensation)."""
   start_requested, start, n_out, delay_compensation = crop
+  audio, impulse_response = aligned16(audio), aligned16(impulse_response)     # (the C entries pick their kernel by these addresses)
   batch_size, audio_size = audio.shape
   batch_size_ir, n_ir_frames, ir_size = impulse_response.shape
   if n_ir_frames == 1 and ir_size > LONG_IR_TAPS:

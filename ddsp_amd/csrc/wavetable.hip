@@ -132,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void wt_fused_kernel(const float* __restr
   double before = block_prefix(fb, j_first, p.F, hop, s_red);
   auto stage = [&](int j, float* __restrict__ dst) {
     const float* __restrict__ src = tb + (size_t)j * W;
-    if ((W & 3) == 0) {
+    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(tb) & 15) == 0) {     // (the caller's tables may start on any 4-byte boundary)
       for (int i = threadIdx.x * 4; i < W; i += kThreads * 4) {
         float4 v = *reinterpret_cast<const float4*>(src + i);
         if (SCALE) { v.x = exp_sigmoid(v.x); v.y = exp_sigmoid(v.y); v.z = exp_sigmoid(v.z); v.w = exp_sigmoid(v.w); }

@@ -200,7 +200,8 @@ def _add(a, b):
   if a.shape != b.shape:
     a, b = torch.broadcast_tensors(a, b)
     a, b = a.contiguous(), b.contiguous()
-  out = torch.empty_like(a)
+  a, b = core.aligned16(a), core.aligned16(b)     # (add_kernel moves float4s: ddsp_add_f32 refuses any other address)
+  out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
   rc = _lib.load().ddsp_add_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), core._stream())
   _lib.check(rc, 'ddsp_add_f32')
   return out

@@ -208,6 +208,7 @@ class Harmonic(processors.Processor):
     n = int(self.n_samples)
     lib = _lib.load()
     dev = amplitudes.device
+    harmonic_distribution = core.aligned16(harmonic_distribution)     # (the direct-sum path picks its kernel by this address)
     audio = torch.empty((b, n), dtype=torch.float32, device=dev)
     ctl_amp = torch.empty_like(amplitudes) if return_outputs_dict else None
     ctl_hd = torch.empty_like(harmonic_distribution) if return_outputs_dict else None
@@ -875,7 +876,7 @@ class FilteredNoise(processors.Processor):
     lib = _lib.load()
     dev = magnitudes.device
     if noise is not None:
-      noise = core.tf_float32(noise)
+      noise = core.aligned16(core.tf_float32(noise))     # (the C entry picks its kernel by this address)
       if tuple(noise.shape) != (b, n):
         raise ValueError('noise must be [{}, {}], got {}'.format(b, n, tuple(noise.shape)))
     if m == 2:
