@@ -181,6 +181,18 @@ SIGNATURES = {
     'ddsp_profile_end': (c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }
 
+# name -> (restype, argtypes) of the entries of csrc/decoder_abi.h (training.nn's layers, training.decoders).  A table of its
+# own for now: tests pin SIGNATURES to include/ddsp_amd.h and to a layout table; decoder_entry() types these on any library object.
+DECODER_SIGNATURES = {
+    'ddsp_bias_norm_act_f32': (c_int, [c_f32p] * 7 + [c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_bias_norm_act_backward_workspace_bytes': (c_size_t, [c_size_t, c_int]),
+    'ddsp_bias_norm_act_backward_f32': (c_int, [c_f32p] * 7 + [c_voidp, c_size_t, c_size_t, c_int, c_int, c_voidp]),
+    'ddsp_gru_forward_workspace_bytes': (c_size_t, [c_int] * 2),
+    'ddsp_gru_forward_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t] + [c_int] * 3 + [c_voidp]),
+    'ddsp_gru_backward_workspace_bytes': (c_size_t, [c_int] * 2),
+    'ddsp_gru_backward_f32': (c_int, [c_f32p] * 8 + [c_voidp, c_size_t] + [c_int] * 3 + [c_voidp]),
+}
+
 # flags (mirror include/ddsp_amd.h)
 HARM_SCALE_EXP_SIGMOID = 0x1
 HARM_NORMALIZE_NYQUIST = 0x2
@@ -217,6 +229,8 @@ CONSISTENCY_MAX_POINTS = 256
 CONSISTENCY_MAX_GAUSSIANS = 4096
 HMM_MAX_PITCHES = 1024                  # states of HmmTranscriber a block holds in registers (csrc/hmm.hip)
 NOTES_SUM = 0x1
+ACTIVATIONS = {'linear': 0, 'leaky_relu': 1, 'relu': 2, 'sigmoid': 3, 'tanh': 4}    # DDSP_ACT_* of csrc/decoder_abi.h
+GRU_MAX_HIDDEN = 2048                   # units of the GRU (csrc/decoder.hip)
 NOTES_MAX_REGIONS = 1024                # regions whose note-on flags get_note_mask's block keeps in LDS (csrc/notes.hip)
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
@@ -255,8 +269,17 @@ def load():
     fn = getattr(lib, name)       # AttributeError here == a declared symbol is not exported
     fn.restype = restype
     fn.argtypes = argtypes
+  for name in DECODER_SIGNATURES:
+    decoder_entry(lib, name)
   _lib = lib
   return lib
+
+
+def decoder_entry(lib, name):
+  """Entry `name` of DECODER_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
+  fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/decoder.hip
+  fn.restype, fn.argtypes = DECODER_SIGNATURES[name]
+  return fn
 
 
 def check(rc, what):

@@ -1,2 +1,5 @@
-"""ddsp.training, as far as it is built: the pure tensor functions of `nn` that pool features over notes."""
+"""ddsp.training, as far as it is built: `nn` (the note pooling and the layers of RnnFcDecoder), `decoders` (RnnFcDecoder) and
+`preprocessing` (the scalings and F0LoudnessPreprocessor)."""
 from ddsp_amd.training import nn
+from ddsp_amd.training import decoders
+from ddsp_amd.training import preprocessing

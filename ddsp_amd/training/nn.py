@@ -1,9 +1,8 @@
-"""The note pooling of ddsp/training/nn.py:357-557 on the MI355X (csrc/notes.hip).
+"""ddsp/training/nn.py on the MI355X: the note pooling (csrc/notes.hip) and the layers RnnFcDecoder is made of (csrc/decoder.hip).
 
-Of the reference's `training.nn` these pure tensor functions exist: straight_through_int_quantization, get_note_mask,
-get_note_mask_from_onset, get_note_lengths, get_note_moments, pool_over_notes and get_short_note_loss_mask - what
-MidiAutoencoder and ZMidiAutoencoder pool their per-note features with.  OUT OF SCOPE: the Keras layers and everything
-else of `training/`.
+NOTE POOLING (ddsp/training/nn.py:357-557): straight_through_int_quantization, get_note_mask, get_note_mask_from_onset,
+get_note_lengths, get_note_moments, pool_over_notes and get_short_note_loss_mask - what MidiAutoencoder and ZMidiAutoencoder pool
+their per-note features with.
 
 The reference builds [batch, time, notes, dims] four times between x and the pooled result; here nothing of that size
 exists, and nothing of size [batch, time, notes] but the mask itself.  The moments and the pooling are exact for ANY fp32
@@ -14,7 +13,19 @@ the variance is exactly 0: every empty region, every one-step note, every consta
 contract here: where a note's variance in a dimension is exactly 0, that entry of the std contributes 0 to dL/dx;
 everywhere else the gradient is the analytic one.  No gradient flows into a mask.
 
-Limits (NotImplementedError): max_regions <= 1024; batch * notes and batch * time below 2 ** 31."""
+Limits (NotImplementedError): max_regions <= 1024; batch * notes and batch * time below 2 ** 31.
+
+LAYERS (ddsp/training/nn.py:48-339, 844-934, 1327-1337): DictLayer, OutputSplitsLayer, ensure_4d, inv_ensure_4d, split_to_dict,
+get_nonlinearity, Fc, FcStack, FcStackOut, Rnn, StatelessRnn, RnnFc, RnnSandwich, over torch.Tensors.  They are torch.nn.Modules
+whose weights are torch.nn.Parameters under the reference's (Keras) names and layouts - Dense: kernel [in, out], bias [out];
+LayerNormalization: gamma, beta, epsilon 1e-3; GRU: kernel [in, 3 H], recurrent_kernel [H, 3 H], bias [2, 3 H], gates z, r, h,
+reset_after - built on the first call or through build(in_ch), with Keras' initialisers.  The matrix products whose M is
+batch * time are torch.matmul (plumbing); bias + LayerNorm + activation and the recurrence are the kernels of csrc/decoder.hip,
+forward and backward.  There is no CPU fallback: without the built library or a GPU the layers raise DdspLibraryError.
+NOT BUILT (ValueError): rnn_type='lstm', bidir=True; and the rest of the reference's nn.py."""
+import inspect
+import math
+
 import torch
 
 from ddsp_amd import _lib
@@ -303,3 +314,510 @@ def get_short_note_loss_mask(note_mask, note_lengths, note_pitches, min_length=4
     raise ValueError('get_short_note_loss_mask: time and notes must be at least 1, got {}'.format(tuple(note_mask.shape)))
   short_notes = ((note_lengths < min_length) & (note_pitches > 0.0)).to(torch.float32)
   return _run_spread(note_mask, short_notes[:, :, None].contiguous())[:, :, 0]
+
+
+# ------------------ the layers of RnnFcDecoder ------------------------------------------------------------------------
+class DictLayer(torch.nn.Module):
+  """Wrap a layer to take dictionary inputs and outputs (ddsp/training/nn.py:48-246).
+
+  A subclass writes `call(self, a, b, c=None) -> ['x', 'y']`; all return values are converted to a dictionary, even if
+  call() returns a tuple.  Without input_keys / output_keys they are inferred from call()'s argument names and return
+  annotation; arguments with defaults become default_input_keys, looked up in the input dictionaries but not required."""
+
+  def __init__(self, input_keys=None, output_keys=None, **kwargs):
+    name = kwargs.pop('name', None)
+    if kwargs:
+      raise TypeError('DictLayer: unknown arguments {}'.format(sorted(kwargs)))
+    super().__init__()
+    self.name = name
+    if not input_keys:
+      input_keys = self.get_argument_names('call')
+      self.default_input_keys = list(self.get_default_argument_names('call'))
+      self.default_input_values = list(self.get_default_argument_values('call'))
+    else:
+      # Manually specifying input keys overwrites default arguments.
+      self.default_input_keys = []
+      self.default_input_values = []
+    output_keys = output_keys or self.get_return_annotations('call')
+    self.input_keys = list(input_keys)
+    self.output_keys = list(output_keys)
+
+  @property
+  def all_input_keys(self):
+    """Full list of inputs and outputs."""
+    return self.input_keys + self.default_input_keys
+
+  @property
+  def n_inputs(self):
+    """Dynamically computed in case input_keys is changed in subclass init."""
+    return len(self.all_input_keys)
+
+  def forward(self, *inputs, **kwargs):
+    return self.call(*inputs, **kwargs)
+
+  def __call__(self, *inputs, **kwargs):
+    """Any dict among `inputs` is merged and input_keys are read out of it ('a/b' looks up nested dicts); tensor arguments come
+    first, then the looked-up keys, then defaults.  Returns call()'s dict, or its outputs under output_keys."""
+    input_dict = {}
+    for v in inputs:
+      if isinstance(v, dict):
+        input_dict.update(v)
+    inputs = [v for v in inputs if not isinstance(v, dict)]
+    for key in self.all_input_keys:
+      if key in kwargs:
+        input_dict[key] = kwargs[key]
+    kwargs = {k: v for k, v in kwargs.items() if k not in self.all_input_keys}
+    for key in self.input_keys:
+      try:
+        inputs.append(core.nested_lookup(key, input_dict))
+      except KeyError:
+        pass
+    for key, value in zip(self.default_input_keys, self.default_input_values):
+      try:
+        inputs.append(core.nested_lookup(key, input_dict))
+      except KeyError:
+        if len(inputs) < self.n_inputs:
+          inputs.append(value)
+    if len(inputs) != self.n_inputs:
+      raise TypeError(f'{len(inputs)} input tensors extracted from inputs'
+                      '(including default args) but the layer expects '
+                      f'{self.n_inputs} tensors.\n'
+                      f'Input keys: {self.input_keys}\n'
+                      f'Default keys: {self.default_input_keys}\n'
+                      f'Default values: {self.default_input_values}\n'
+                      f'Input dictionaries: {input_dict}\n'
+                      f'Input Tensors (Args, Dicts, and Defaults): {inputs}\n')
+    outputs = super().__call__(*inputs, **kwargs)
+    if isinstance(outputs, dict):
+      return outputs
+    outputs = core.make_iterable(outputs)
+    if len(self.output_keys) != len(outputs):
+      raise ValueError(f'Output keys ({self.output_keys}) must have the same'
+                       f'length as outputs ({outputs})')
+    return dict(zip(self.output_keys, outputs))
+
+  def get_argument_names(self, method):
+    """Get list of strings for names of required arguments to method."""
+    spec = inspect.getfullargspec(getattr(self, method))
+    if spec.defaults:
+      return spec.args[1:-len(spec.defaults)]
+    return spec.args[1:]
+
+  def get_default_argument_names(self, method):
+    """Get list of strings for names of default arguments to method."""
+    spec = inspect.getfullargspec(getattr(self, method))
+    return spec.args[-len(spec.defaults):] if spec.defaults else []
+
+  def get_default_argument_values(self, method):
+    """Get list of default values of the default arguments to method."""
+    spec = inspect.getfullargspec(getattr(self, method))
+    return spec.defaults if spec.defaults else []
+
+  def get_return_annotations(self, method):
+    """Get list of strings of return annotations of method."""
+    spec = inspect.getfullargspec(getattr(self, method))
+    return core.make_iterable(spec.annotations['return'])
+
+
+# ------------------------ Shapes ----------------------------------------------
+def ensure_4d(x):
+  """Add extra dimensions to make sure tensor has height and width."""
+  if x.dim() == 2:
+    return x[:, None, None, :]
+  if x.dim() == 3:
+    return x[:, :, None, :]
+  return x
+
+
+def inv_ensure_4d(x, n_dims):
+  """Remove excess dims, inverse of ensure_4d() function."""
+  if n_dims == 2:
+    return x[:, 0, 0, :]
+  if n_dims == 3:
+    return x[:, :, 0, :]
+  return x
+
+
+# ------------------ Utilities -------------------------------------------------
+def split_to_dict(tensor, tensor_splits):
+  """Split a tensor into a dictionary of multiple tensors."""
+  labels = [v[0] for v in tensor_splits]
+  sizes = [int(v[1]) for v in tensor_splits]
+  return dict(zip(labels, torch.split(tensor, sizes, dim=-1)))
+
+
+NONLINEARITIES = {
+    'leaky_relu': lambda x: torch.nn.functional.leaky_relu(x, 0.2),       # tf.nn.leaky_relu's slope
+    'relu': torch.relu,
+    'sigmoid': torch.sigmoid,
+    'tanh': torch.tanh,
+    'linear': lambda x: x,
+}
+
+
+def _activation_code(nonlinearity):
+  if nonlinearity not in _lib.ACTIVATIONS:
+    raise ValueError('nonlinearity {!r} is not supported; supported: {}'.format(nonlinearity, sorted(_lib.ACTIVATIONS)))
+  return _lib.ACTIVATIONS[nonlinearity]
+
+
+def get_nonlinearity(nonlinearity):
+  """Get nonlinearity function by name: 'leaky_relu' (slope 0.2), 'relu', 'sigmoid', 'tanh', 'linear' (framework ops; the Fc
+  layers run the same functions inside their kernel)."""
+  _activation_code(nonlinearity)
+  return NONLINEARITIES[nonlinearity]
+
+
+_norm_ws = core.Workspace()
+_gru_ws = core.Workspace()
+LAYER_NORM_EPSILON = 1e-3            # tf.keras.layers.LayerNormalization's default
+
+
+def _decoder_entry(name):
+  return _lib.decoder_entry(_lib.load(), name)
+
+
+def _checked(rc, what):
+  if rc == _lib.ERR_UNSUPPORTED:
+    raise ValueError('{}: beyond the limits of the MI355X path (DDSP_ERR_UNSUPPORTED)'.format(what))
+  _lib.check(rc, what)
+
+
+class _BiasNormActFunction(torch.autograd.Function):
+  """torch.autograd node of act(gamma * LayerNorm(x + bias) + beta) over the last axis of x [rows, ch] (plumbing: both
+  directions are C-ABI calls).  Kept for the backward: xhat, rstd, gamma, beta."""
+
+  @staticmethod
+  def forward(ctx, x, bias, gamma, beta, act, eps):
+    needs = not isinstance(ctx, core._NoCtx)
+    rows, ch = x.shape
+    y = torch.empty_like(x)
+    xhat = torch.empty_like(x) if needs else None
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if needs else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    rc = _decoder_entry('ddsp_bias_norm_act_f32')(x.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                                  ptr(xhat), ptr(rstd), rows, ch, act, eps, core._stream())
+    _checked(rc, 'ddsp_bias_norm_act_f32')
+    ctx.save_for_backward(xhat, rstd, gamma, beta)
+    ctx.act = act
+    return y
+
+  @staticmethod
+  def backward(ctx, grad_y):
+    xhat, rstd, gamma, beta = ctx.saved_tensors
+    rows, ch = xhat.shape
+    grad_y = core.tf_float32(grad_y)
+    dx = torch.empty_like(xhat)
+    dparams = torch.empty((3, ch), dtype=torch.float32, device=xhat.device)
+    ws = _norm_ws.get(_decoder_entry('ddsp_bias_norm_act_backward_workspace_bytes')(rows, ch), xhat.device)
+    rc = _decoder_entry('ddsp_bias_norm_act_backward_f32')(grad_y.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                                           beta.data_ptr(), dx.data_ptr(), dparams.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                           rows, ch, ctx.act, core._stream())
+    _checked(rc, 'ddsp_bias_norm_act_backward_f32')
+    return dx, dparams[2], dparams[0], dparams[1], None, None
+
+
+def bias_norm_act(x, bias, gamma, beta, nonlinearity='linear', epsilon=LAYER_NORM_EPSILON):
+  """nonlinearity(gamma * (v - mean(v)) / sqrt(var(v) + epsilon) + beta), v = x + bias, moments over the last axis (biased
+  variance, two passes): one kernel each way instead of the dozen elementwise and reduction ops of the framework chain.
+  Differentiable in x, bias, gamma and beta; a row of equal values gives xhat = 0 and a finite gradient."""
+  act = _activation_code(nonlinearity)
+  x, bias, gamma, beta = core.tf_float32(x), core.tf_float32(bias), core.tf_float32(gamma), core.tf_float32(beta)
+  ch = x.shape[-1] if x.dim() else 0
+  if x.dim() < 1 or ch < 1 or tuple(bias.shape) != (ch,) or tuple(gamma.shape) != (ch,) or tuple(beta.shape) != (ch,):
+    raise ValueError('bias_norm_act: x must be [..., ch] with ch >= 1 and bias, gamma, beta [ch], got {}, {}, {}, {}'.format(
+        tuple(x.shape), tuple(bias.shape), tuple(gamma.shape), tuple(beta.shape)))
+  flat = x.reshape(-1, ch)
+  if core._needs_grad(flat, bias, gamma, beta):
+    y = _BiasNormActFunction.apply(flat, bias, gamma, beta, act, float(epsilon))
+  else:
+    y = _BiasNormActFunction.forward(core._NoCtx(), flat, bias, gamma, beta, act, float(epsilon))
+  return y.reshape(x.shape)
+
+
+class _GruFunction(torch.autograd.Function):
+  """torch.autograd node of the recurrence: (mx [b, t, 3 H], recurrent_kernel [H, 3 H], recurrent bias [3 H], h0 [b, H]) ->
+  y [b, t, H].  Both scans are C-ABI calls, one launch per step; the recurrent weight gradients are matrix products over all
+  steps at once.  Kept for the backward: y, h0, the recurrent kernel and z, r, hh, mh_h of every step (batch * time * 4 H floats)."""
+
+  @staticmethod
+  def forward(ctx, mx, rk, rb, h0):
+    needs = not isinstance(ctx, core._NoCtx)
+    b, t, h3 = mx.shape
+    h = h3 // 3
+    y = torch.empty((b, t, h), dtype=torch.float32, device=mx.device)
+    saved = torch.empty((4, b, t, h), dtype=torch.float32, device=mx.device) if needs else None
+    if b:
+      ws = _gru_ws.get(_decoder_entry('ddsp_gru_forward_workspace_bytes')(b, h), mx.device)
+      rc = _decoder_entry('ddsp_gru_forward_f32')(mx.data_ptr(), rk.data_ptr(), rb.data_ptr(), h0.data_ptr(), y.data_ptr(),
+                                                  None if saved is None else saved.data_ptr(), ws.data_ptr(), ws.numel(), b, t, h,
+                                                  core._stream())
+      _checked(rc, 'ddsp_gru_forward_f32')
+    ctx.save_for_backward(y, h0, saved, rk)
+    return y
+
+  @staticmethod
+  def backward(ctx, grad_y):
+    y, h0, saved, rk = ctx.saved_tensors
+    b, t, h = y.shape
+    grad_y = core.tf_float32(grad_y)
+    d_in = torch.empty((b, t, 3 * h), dtype=torch.float32, device=y.device)
+    d_rec = torch.empty_like(d_in)
+    dh0 = torch.empty_like(h0)
+    if b:
+      ws = _gru_ws.get(_decoder_entry('ddsp_gru_backward_workspace_bytes')(b, h), y.device)
+      rc = _decoder_entry('ddsp_gru_backward_f32')(grad_y.data_ptr(), y.data_ptr(), h0.data_ptr(), saved.data_ptr(), rk.data_ptr(),
+                                                   d_in.data_ptr(), d_rec.data_ptr(), dh0.data_ptr(), ws.data_ptr(), ws.numel(), b, t, h,
+                                                   core._stream())
+      _checked(rc, 'ddsp_gru_backward_f32')
+    h_prev = torch.cat([h0[:, None, :], y[:, :-1, :]], dim=1).reshape(b * t, h)
+    flat_rec = d_rec.reshape(b * t, 3 * h)
+    return d_in, torch.matmul(h_prev.t(), flat_rec), flat_rec.sum(0), dh0
+
+
+def gru_recurrence(mx, recurrent_kernel, recurrent_bias, initial_state=None):
+  """The Keras GRU loop (reset_after=True, gates z, r, h) on a given input projection mx = x kernel + bias[0]:
+  mh = h recurrent_kernel + recurrent_bias; z = sigmoid(mx_z + mh_z); r = sigmoid(mx_r + mh_r); hh = tanh(mx_h + r mh_h);
+  h' = z h + (1 - z) hh.  -> all states [batch, time, H].  Differentiable in every argument.  One launch per step each way; the
+  same bits on every run and for any subset of the batch rows.  H up to 2048 (ValueError beyond); on the matrix-core path
+  (H a multiple of 16) the initial state must lie inside fp16's range."""
+  mx, rk, rb = core.tf_float32(mx), core.tf_float32(recurrent_kernel), core.tf_float32(recurrent_bias)
+  if mx.dim() != 3 or mx.shape[1] < 1 or mx.shape[2] < 3 or mx.shape[2] % 3:
+    raise ValueError('gru_recurrence: mx must be [batch, time >= 1, 3 H], got {}'.format(tuple(mx.shape)))
+  b, _, h3 = mx.shape
+  h = h3 // 3
+  if tuple(rk.shape) != (h, h3) or tuple(rb.shape) != (h3,):
+    raise ValueError('gru_recurrence: recurrent_kernel must be [H, 3 H] and recurrent_bias [3 H] for H = {}, got {} and {}'.format(
+        h, tuple(rk.shape), tuple(rb.shape)))
+  if h > _lib.GRU_MAX_HIDDEN:
+    raise ValueError('gru_recurrence: at most {} units on the MI355X path, got {}'.format(_lib.GRU_MAX_HIDDEN, h))
+  if initial_state is None:
+    h0 = torch.zeros((b, h), dtype=torch.float32, device=mx.device)
+  else:
+    h0 = core.tf_float32(initial_state)
+    if tuple(h0.shape) != (b, h):
+      raise ValueError('gru_recurrence: the initial state must be [batch, H] = {}, got {}'.format((b, h), tuple(h0.shape)))
+  if core._needs_grad(mx, rk, rb, h0):
+    return _GruFunction.apply(mx, rk, rb, h0)
+  return _GruFunction.forward(core._NoCtx(), mx, rk, rb, h0)
+
+
+def _glorot_uniform(fan_in, fan_out):
+  limit = math.sqrt(6.0 / (fan_in + fan_out))
+  return torch.empty((fan_in, fan_out), dtype=torch.float32).uniform_(-limit, limit)
+
+
+class _Lazy(torch.nn.Module):
+  """Weights are made on the first call, when the input width is known, or by build(in_ch)."""
+
+  def __init__(self):
+    super().__init__()
+    self.built = False
+
+  def _ensure_built(self, in_ch):
+    if not self.built:
+      self.build(int(in_ch))
+
+  def _param(self, value):
+    return torch.nn.Parameter(value.to(core._device()))
+
+
+class Dense(_Lazy):
+  """tf.keras.layers.Dense(units): x kernel + bias; kernel [in, out] glorot-uniform, bias [out] zeros.  The product is
+  torch.addmm (plumbing)."""
+
+  def __init__(self, units):
+    super().__init__()
+    self.units = int(units)
+
+  def build(self, in_ch):
+    self.kernel = self._param(_glorot_uniform(in_ch, self.units))
+    self.bias = self._param(torch.zeros(self.units))
+    self.built = True
+
+  def project(self, x):
+    """x kernel, without the bias (Fc's kernel adds it): [..., in] -> [rows, out]."""
+    x = core.aligned16(core.tf_float32(x))           # the framework's product may not pick its kernel by the address
+    self._ensure_built(x.shape[-1])
+    return torch.matmul(x.reshape(-1, x.shape[-1]), self.kernel), x.shape[:-1] + (self.units,)
+
+  def forward(self, x):
+    flat, shape = self.project(x)
+    return (flat + self.bias).reshape(shape)
+
+
+class LayerNormalization(_Lazy):
+  """tf.keras.layers.LayerNormalization() over the last axis: gamma (ones), beta (zeros), epsilon 1e-3, biased variance."""
+
+  def __init__(self, epsilon=LAYER_NORM_EPSILON):
+    super().__init__()
+    self.epsilon = float(epsilon)
+
+  def build(self, in_ch):
+    self.gamma = self._param(torch.ones(in_ch))
+    self.beta = self._param(torch.zeros(in_ch))
+    self.built = True
+
+  def forward(self, x):
+    x = core.tf_float32(x)
+    self._ensure_built(x.shape[-1])
+    return bias_norm_act(x, torch.zeros_like(self.beta), self.gamma, self.beta, 'linear', self.epsilon)
+
+
+class GRU(_Lazy):
+  """tf.keras.layers.GRU(units, return_sequences, return_state): kernel [in, 3 H] glorot-uniform, recurrent_kernel [H, 3 H]
+  orthogonal, bias [2, 3 H] zeros (row 0 input bias, row 1 recurrent bias), gates z, r, h, reset_after=True, zero initial state
+  unless one is given.  The input projection of all steps is one torch.addmm; the recurrence is gru_recurrence."""
+
+  def __init__(self, units, return_sequences=False, return_state=False):
+    super().__init__()
+    self.units = int(units)
+    self.return_sequences = bool(return_sequences)
+    self.return_state = bool(return_state)
+
+  def build(self, in_ch):
+    h = self.units
+    self.kernel = self._param(_glorot_uniform(in_ch, 3 * h))
+    self.recurrent_kernel = self._param(torch.nn.init.orthogonal_(torch.empty((h, 3 * h), dtype=torch.float32)))
+    self.bias = self._param(torch.zeros((2, 3 * h)))
+    self.built = True
+
+  def forward(self, x, initial_state=None):
+    x = core.aligned16(core.tf_float32(x))
+    if x.dim() != 3:
+      raise ValueError('GRU: x must be [batch, time, channels], got {}'.format(tuple(x.shape)))
+    self._ensure_built(x.shape[-1])
+    b, t, ch = x.shape
+    mx = torch.addmm(self.bias[0], x.reshape(b * t, ch), self.kernel).reshape(b, t, 3 * self.units)
+    y = gru_recurrence(mx, self.recurrent_kernel, self.bias[1], initial_state)
+    state = y[:, -1, :]
+    out = y if self.return_sequences else state
+    return (out, state) if self.return_state else out
+
+
+# ---------------- Stacks ------------------------------------------------------
+class _Sequential(torch.nn.Module):
+  def __init__(self, layers):
+    super().__init__()
+    self.layers = torch.nn.ModuleList(layers)
+
+  def forward(self, x):
+    for layer in self.layers:
+      x = layer(x)
+    return x
+
+
+class Fc(_Lazy):
+  """Makes a Dense -> LayerNorm -> Leaky ReLU layer (ddsp/training/nn.py:844-853): torch.matmul, then ONE kernel for
+  bias + LayerNorm + activation.  Weights: dense.kernel, dense.bias, layer_norm.gamma, layer_norm.beta."""
+
+  def __init__(self, ch=128, nonlinearity='leaky_relu'):
+    super().__init__()
+    _activation_code(nonlinearity)
+    self.nonlinearity = nonlinearity
+    self.dense = Dense(ch)
+    self.layer_norm = LayerNormalization()
+
+  def build(self, in_ch):
+    self.dense.build(in_ch)
+    self.layer_norm.build(self.dense.units)
+    self.built = True
+
+  def forward(self, x):
+    x = core.tf_float32(x)
+    self._ensure_built(x.shape[-1])
+    flat, shape = self.dense.project(x)
+    return bias_norm_act(flat, self.dense.bias, self.layer_norm.gamma, self.layer_norm.beta, self.nonlinearity,
+                         self.layer_norm.epsilon).reshape(shape)
+
+
+class FcStack(_Sequential):
+  """Stack Dense -> LayerNorm -> Leaky ReLU layers."""
+
+  def __init__(self, ch=256, layers=2, nonlinearity='leaky_relu'):
+    super().__init__([Fc(ch, nonlinearity) for _ in range(layers)])
+
+
+def _gru_only(rnn_type, bidir=False):
+  if rnn_type not in ('gru', 'lstm'):
+    raise ValueError("rnn_type must be 'gru' or 'lstm', got {!r}".format(rnn_type))
+  if rnn_type == 'lstm':
+    raise ValueError("rnn_type='lstm' is not built on the MI355X path; only 'gru' is")
+  if bidir:
+    raise ValueError('bidir=True is not built on the MI355X path; only the forward GRU is')
+
+
+class Rnn(torch.nn.Module):
+  """Single RNN layer (ddsp/training/nn.py:866-879).  Only rnn_type='gru' with bidir=False is built (ValueError otherwise)."""
+
+  def __init__(self, dims, rnn_type, return_sequences=True, bidir=False):
+    super().__init__()
+    _gru_only(rnn_type, bidir)
+    self.rnn = GRU(dims, return_sequences=return_sequences)
+
+  def forward(self, x):
+    return self.rnn(x)
+
+
+class StatelessRnn(torch.nn.Module):
+  """Stateless unidirectional RNN for streaming models (ddsp/training/nn.py:883-904)."""
+
+  def __init__(self, dims, rnn_type):
+    super().__init__()
+    _gru_only(rnn_type)
+    self.rnn = GRU(dims, return_sequences=True, return_state=True)
+
+  def forward(self, x, state):
+    """x [batch, T, dims_in], state [batch, dims] (the last output) -> y [batch, T, dims], new_state [batch, dims]."""
+    y, new_state = self.rnn(x, initial_state=state)
+    return y, new_state
+
+
+class RnnFc(_Sequential):
+  """RNN layer -> fully connected -> LayerNorm -> Activation fn (ddsp/training/nn.py:908-916).  The reference hands `bidir` to
+  Rnn's third positional argument, which is return_sequences; here it goes where its name says and every Rnn returns sequences."""
+
+  def __init__(self, rnn_feat, out_feat, rnn_type='lstm', nonlinearity='sigmoid', bidir=False, n_rnn=1):
+    layers = [Rnn(rnn_feat, rnn_type, bidir=bidir) for _ in range(n_rnn)]
+    layers.append(Fc(out_feat, nonlinearity=nonlinearity))
+    super().__init__(layers)
+
+
+class RnnSandwich(_Sequential):
+  """RNN Sandwiched by two FC Stacks."""
+
+  def __init__(self, fc_stack_ch=256, fc_stack_layers=2, rnn_ch=512, rnn_type='gru'):
+    super().__init__([FcStack(fc_stack_ch, fc_stack_layers), Rnn(rnn_ch, rnn_type), FcStack(fc_stack_ch, fc_stack_layers)])
+
+
+class FcStackOut(torch.nn.Module):
+  """Stack of FC layers with variable hidden and output dims."""
+
+  def __init__(self, ch, layers, n_out):
+    super().__init__()
+    self.stack = FcStack(ch, layers)
+    self.dense_out = Dense(n_out)
+
+  def forward(self, x):
+    return self.dense_out(self.stack(x))
+
+
+class OutputSplitsLayer(DictLayer):
+  """A DictLayer that splits an output tensor into a dictionary of tensors (ddsp/training/nn.py:249-298): a subclass writes
+  compute_output(*inputs) -> one tensor, which runs through a final Dense and is split according to output_splits."""
+
+  def __init__(self, input_keys=None, output_splits=(('amps', 1), ('harmonic_distribution', 40)), **kwargs):
+    input_keys = input_keys or self.get_argument_names('compute_output')
+    super().__init__(input_keys=input_keys, output_keys=[v[0] for v in output_splits], **kwargs)
+    self.output_splits = output_splits
+    self.n_out = sum([v[1] for v in output_splits])
+    self.dense_out = Dense(self.n_out)
+
+  def call(self, *inputs, **unused_kwargs):
+    """Run compute_output(), dense output layer, then split to a dictionary."""
+    output = self.compute_output(*inputs)
+    return split_to_dict(self.dense_out(output), self.output_splits)
+
+  def compute_output(self, *inputs):
+    """Takes tensors as input, runs network, and outputs a single tensor (usually [batch, time, channels])."""
+    raise NotImplementedError
