@@ -193,6 +193,15 @@ DECODER_SIGNATURES = {
     'ddsp_gru_backward_f32': (c_int, [c_f32p] * 8 + [c_voidp, c_size_t] + [c_int] * 3 + [c_voidp]),
 }
 
+# name -> (restype, argtypes) of the entries of csrc/norm_abi.h (training.nn's normalize_op / Normalize), typed by norm_entry():
+# a table of its own for the same reason.
+NORM_SIGNATURES = {
+    'ddsp_group_norm_workspace_bytes': (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
+    'ddsp_group_norm_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t, c_size_t, c_size_t, c_int, c_int, c_float, c_voidp]),
+    'ddsp_group_norm_backward_workspace_bytes': (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
+    'ddsp_group_norm_backward_f32': (c_int, [c_f32p] * 8 + [c_voidp, c_size_t, c_size_t, c_size_t, c_int, c_int, c_voidp]),
+}
+
 # flags (mirror include/ddsp_amd.h)
 HARM_SCALE_EXP_SIGMOID = 0x1
 HARM_NORMALIZE_NYQUIST = 0x2
@@ -271,6 +280,8 @@ def load():
     fn.argtypes = argtypes
   for name in DECODER_SIGNATURES:
     decoder_entry(lib, name)
+  for name in NORM_SIGNATURES:
+    norm_entry(lib, name)
   _lib = lib
   return lib
 
@@ -279,6 +290,13 @@ def decoder_entry(lib, name):
   """Entry `name` of DECODER_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
   fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/decoder.hip
   fn.restype, fn.argtypes = DECODER_SIGNATURES[name]
+  return fn
+
+
+def norm_entry(lib, name):
+  """Entry `name` of NORM_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
+  fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/group_norm.hip
+  fn.restype, fn.argtypes = NORM_SIGNATURES[name]
   return fn
 
 

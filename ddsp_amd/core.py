@@ -315,7 +315,8 @@ def angular_cumsum(angular_frequency, chunk_size=1000):
 # --------------------------------------------------------------------------------------
 def resample(inputs, n_timesteps, method='linear', add_endpoint=True):
   """core.resample (ddsp/core.py:573-642): [n_frames] / [B, n_frames] / [B, n_frames, C] /
-  [B, n_frames, n_freq, C] -> n_timesteps along time; methods 'nearest', 'linear', 'cubic', 'window'."""
+  [B, n_frames, n_freq, C] -> n_timesteps along time; methods 'nearest', 'linear', 'cubic', 'window'.  Differentiable in the
+  input (the adjoint kernel, ddsp_resample_ex_backward_f32); the forward is the same call, to the bit, with or without a gradient."""
   inputs = tf_float32(inputs)
   is_1d, is_2d, is_4d = inputs.dim() == 1, inputs.dim() == 2, inputs.dim() == 4
   if is_1d:
@@ -364,12 +365,40 @@ def upsample_with_windows(inputs, n_timesteps, add_endpoint=True):
   return _resample_call(inputs, int(n_timesteps), 'window', add_endpoint)
 
 
+class _ResampleFunction(torch.autograd.Function):
+  """torch.autograd node of core.resample / upsample_with_windows on [B,F,C] (plumbing: both directions are C-ABI calls).
+  Resampling is linear in its input: the backward is the adjoint kernel (ddsp_resample_ex_backward_f32), a gather with a fixed
+  order of additions.  Nothing is kept for it but the shape."""
+
+  @staticmethod
+  def forward(ctx, inputs, n_timesteps, method, add_endpoint):
+    ctx.args = (tuple(inputs.shape), n_timesteps, method, add_endpoint)
+    return _resample_run(inputs, n_timesteps, method, add_endpoint)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    (b, f, c), n_timesteps, method, add_endpoint = ctx.args
+    grad_out = tf_float32(grad_out)
+    grad_in = torch.empty((b, f, c), dtype=torch.float32, device=grad_out.device)
+    if b and c:
+      rc = _lib.load().ddsp_resample_ex_backward_f32(grad_out.data_ptr(), grad_in.data_ptr(), b, f, n_timesteps, c,
+                                                     _lib.RESAMPLE_METHODS[method], 1 if add_endpoint else 0, _stream())
+      _lib.check(rc, 'ddsp_resample_ex_backward_f32')
+    return grad_in, None, None, None
+
+
 def _resample_call(inputs, n_timesteps, method, add_endpoint):
+  """[B,F,C] -> [B,N,C], differentiable in the input: the same forward call with or without a gradient."""
+  inputs = inputs.contiguous()
+  if _needs_grad(inputs):
+    return _ResampleFunction.apply(inputs, n_timesteps, method, add_endpoint)
+  return _resample_run(inputs, n_timesteps, method, add_endpoint)
+
+
+def _resample_run(inputs, n_timesteps, method, add_endpoint):
   """[B,F,C] -> [B,N,C]: 'linear' / 'window' with the endpoint go to the stand-alone kernel of the hot
   path's own forms (ddsp_resample_f32), every other combination to the general one (ddsp_resample_ex_f32)."""
-  inputs = inputs.contiguous()
   b, f, c = inputs.shape
-  require_no_grad('core.resample / upsample_with_windows', inputs)
   out = torch.empty((b, n_timesteps, c), dtype=torch.float32, device=inputs.device)
   if b == 0 or c == 0:
     return out

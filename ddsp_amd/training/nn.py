@@ -1,4 +1,5 @@
-"""ddsp/training/nn.py on the MI355X: the note pooling (csrc/notes.hip) and the layers RnnFcDecoder is made of (csrc/decoder.hip).
+"""ddsp/training/nn.py on the MI355X: the note pooling (csrc/notes.hip), the layers RnnFcDecoder is made of (csrc/decoder.hip) and
+the normalisations the encoders use (csrc/group_norm.hip).
 
 NOTE POOLING (ddsp/training/nn.py:357-557): straight_through_int_quantization, get_note_mask, get_note_mask_from_onset,
 get_note_lengths, get_note_moments, pool_over_notes and get_short_note_loss_mask - what MidiAutoencoder and ZMidiAutoencoder pool
@@ -22,7 +23,13 @@ LayerNormalization: gamma, beta, epsilon 1e-3; GRU: kernel [in, 3 H], recurrent_
 reset_after - built on the first call or through build(in_ch), with Keras' initialisers.  The matrix products whose M is
 batch * time are torch.matmul (plumbing); bias + LayerNorm + activation and the recurrence are the kernels of csrc/decoder.hip,
 forward and backward.  There is no CPU fallback: without the built library or a GPU the layers raise DdspLibraryError.
-NOT BUILT (ValueError): rnn_type='lstm', bidir=True; and the rest of the reference's nn.py."""
+NOT BUILT (ValueError): rnn_type='lstm', bidir=True; and the rest of the reference's nn.py.
+
+NORMALISATION (ddsp/training/nn.py:561-611, 1065-1136): normalize_op, Normalize, ConditionalScaleAndShift, ConditionalNorm,
+get_norm, Identity, get_embedding.  normalize_op - instance, layer or group normalisation of a channel-last [batch, h, w, ch]
+tensor, eps 1e-5 - and Normalize's scale and shift run in ONE kernel each way (csrc/group_norm.hip; C ABI csrc/norm_abi.h):
+two-pass moments, nothing activation-sized kept for the backward but x itself, no atomics, the same bits for a batch row alone
+and inside a batch.  The conditional scale and shift and the embedding's gather are framework ops."""
 import inspect
 import math
 
@@ -693,6 +700,190 @@ class GRU(_Lazy):
     state = y[:, -1, :]
     out = y if self.return_sequences else state
     return (out, state) if self.return_state else out
+
+
+# ------------------ Normalization ---------------------------------------------
+_group_norm_ws = core.Workspace()
+NORMALIZE_EPSILON = 1e-5             # normalize_op's default
+
+
+def _norm_entry(name):
+  return _lib.norm_entry(_lib.load(), name)
+
+
+class _GroupNormFunction(torch.autograd.Function):
+  """torch.autograd node of group normalisation over x [N, S, C] with optional scale / shift [C] (plumbing: both directions are
+  C-ABI calls).  Kept for the backward: x, scale and the [N, G] means and rstds - no activation-sized xhat."""
+
+  @staticmethod
+  def forward(ctx, x, scale, shift, groups, eps):
+    needs = not isinstance(ctx, core._NoCtx)
+    n, s, c = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty((n, groups), dtype=torch.float32, device=x.device) if needs else None
+    rstd = torch.empty((n, groups), dtype=torch.float32, device=x.device) if needs else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    if n:
+      ws = _group_norm_ws.get(_norm_entry('ddsp_group_norm_workspace_bytes')(n, s, c, groups), x.device)
+      rc = _norm_entry('ddsp_group_norm_f32')(x.data_ptr(), ptr(scale), ptr(shift), y.data_ptr(), ptr(mean), ptr(rstd), ws.data_ptr(),
+                                              ws.numel(), n, s, c, groups, eps, core._stream())
+      _checked(rc, 'ddsp_group_norm_f32')
+    ctx.save_for_backward(x, scale, mean, rstd)
+    ctx.groups = groups
+    return y
+
+  @staticmethod
+  def backward(ctx, grad_y):
+    x, scale, mean, rstd = ctx.saved_tensors
+    n, s, c = x.shape
+    grad_y = core.tf_float32(grad_y)
+    dx = torch.empty_like(x)
+    dscale = torch.empty_like(scale) if scale is not None else None
+    dshift = torch.empty_like(scale) if scale is not None else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    ws = _group_norm_ws.get(_norm_entry('ddsp_group_norm_backward_workspace_bytes')(n, s, c, ctx.groups), x.device)
+    rc = _norm_entry('ddsp_group_norm_backward_f32')(grad_y.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ptr(scale),
+                                                     dx.data_ptr(), ptr(dscale), ptr(dshift), ws.data_ptr(), ws.numel(), n, s, c,
+                                                     ctx.groups, core._stream())
+    _checked(rc, 'ddsp_group_norm_backward_f32')
+    return dx, dscale, dshift, None, None
+
+
+def _group_norm(x, norm_type, scale=None, shift=None, eps=NORMALIZE_EPSILON):
+  """x [batch, h, w, ch] of any layout or dtype, scale / shift [ch] or None -> the normalised tensor, one kernel each way.  The
+  arguments are checked before anything touches the device."""
+  shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(torch.as_tensor(x).shape)
+  if len(shape) != 4:
+    raise ValueError('normalize_op: x must be [batch, height, width, channels], got {}'.format(shape))
+  b, h, w, ch = shape
+  n_groups = {'instance': ch, 'layer': 1, 'group': 32}[norm_type]
+  if min(h, w, ch) < 1:
+    raise ValueError('normalize_op: height, width and channels must be at least 1, got {}'.format(shape))
+  if ch % n_groups:
+    raise ValueError("normalize_op: norm_type='group' takes channels in multiples of 32, got {}".format(ch))
+  x = core.tf_float32(x)
+  flat = x.reshape(b, h * w, ch)
+  if core._needs_grad(flat, scale, shift):
+    y = _GroupNormFunction.apply(flat, scale, shift, n_groups, float(eps))
+  else:
+    y = _GroupNormFunction.forward(core._NoCtx(), flat, scale, shift, n_groups, float(eps))
+  return y.reshape(x.shape)
+
+
+def normalize_op(x, norm_type='layer', eps=1e-5):
+  """Apply either Group, Instance, or Layer normalization, or None (ddsp/training/nn.py:561-575).
+
+  x [batch, height, width, channels] of any layout or dtype; moments (biased variance) over height, width and the channels of a
+  group, per batch row: 'instance' has a group per channel, 'layer' one group, 'group' 32 groups of adjacent channels
+  (ValueError unless channels is a multiple of 32); an unknown norm_type raises the reference's KeyError; None returns x.
+  (x - mean) / sqrt(var + eps), one kernel of csrc/group_norm.hip each way.  Differentiable in x.  A group of equal values
+  gives 0 and a finite gradient.  batch * height * width * channels must stay below 2 ** 31 (ValueError)."""
+  if norm_type is None:
+    return x
+  return _group_norm(x, norm_type, eps=eps)
+
+
+class Normalize(_Lazy):
+  """Normalization layer with learnable parameters (ddsp/training/nn.py:578-603): normalize_op, then * scale + shift, fused into
+  the one kernel.  Weights: scale (ones) and shift (zeros), both [1, 1, 1, ch] as Keras holds them."""
+
+  def __init__(self, norm_type='layer'):
+    super().__init__()
+    self.norm_type = norm_type
+
+  def build(self, in_ch):
+    self.scale = self._param(torch.ones((1, 1, 1, in_ch)))
+    self.shift = self._param(torch.zeros((1, 1, 1, in_ch)))
+    self.built = True
+
+  def forward(self, x):
+    x = core.tf_float32(x)
+    self._ensure_built(x.shape[-1])
+    n_dims = x.dim()
+    x = ensure_4d(x)
+    if self.norm_type is not None:
+      x = _group_norm(x, self.norm_type, self.scale.reshape(-1), self.shift.reshape(-1))
+    else:
+      x = (x * self.scale) + self.shift
+    return inv_ensure_4d(x, n_dims)
+
+
+class ConditionalScaleAndShift(_Lazy):
+  """Conditional scaling and shifting after normalization (ddsp/training/nn.py:1075-1099): (x, z) -> x * scale(z) + shift(z),
+  or x + shift(z) with shift_only; scale and shift are the halves of one Dense of z.  Framework ops."""
+
+  def __init__(self, shift_only=False):
+    super().__init__()
+    self.shift_only = shift_only
+    self.dense = None
+
+  def build(self, in_ch):
+    self.x_ch = int(in_ch)
+    self.dense = Dense(self.x_ch if self.shift_only else 2 * self.x_ch)
+    self.built = True
+
+  def forward(self, inputs):
+    x, z = inputs
+    self._ensure_built(x.shape[-1])
+    if self.shift_only:
+      return x + self.dense(z)
+    scale_shift = self.dense(z)
+    return (x * scale_shift[..., :self.x_ch]) + scale_shift[..., self.x_ch:]
+
+
+class ConditionalNorm(torch.nn.Module):
+  """Apply normalization and then conditional scale and shift (ddsp/training/nn.py:1102-1136).
+
+  inputs: the pair (x [batch, height, width, ch], z broadcastable to it); norm_type 'group', 'instance' or 'layer'."""
+
+  def __init__(self, norm_type='instance', shift_only=False):
+    super().__init__()
+    self.norm_type = norm_type
+    self.conditional_scale_and_shift = ConditionalScaleAndShift(shift_only=shift_only)
+
+  def forward(self, inputs):
+    x, z = inputs
+    x = normalize_op(x, norm_type=self.norm_type)
+    return self.conditional_scale_and_shift([x, z])
+
+
+def get_norm(norm_type, conditional, shift_only):
+  """Helper function to get conditional norm if needed."""
+  if conditional:
+    return ConditionalNorm(norm_type=norm_type, shift_only=shift_only)
+  return Normalize(norm_type)
+
+
+class Identity(torch.nn.Module):
+  """Utility identity layer."""
+
+  def forward(self, x):
+    return x
+
+
+# ------------------ Embeddings ------------------------------------------------
+class Embedding(_Lazy):
+  """tf.keras.layers.Embedding(input_dim, output_dim): weight `embeddings` [input_dim, output_dim], uniform in +-0.05; integer ids of
+  any shape -> [..., output_dim], a framework gather."""
+
+  def __init__(self, input_dim, output_dim):
+    super().__init__()
+    self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+
+  def build(self, unused_in_ch=None):
+    self.embeddings = self._param(torch.empty((self.input_dim, self.output_dim), dtype=torch.float32).uniform_(-0.05, 0.05))
+    self.built = True
+
+  def forward(self, ids):
+    if not self.built:
+      self.build()
+    ids = torch.as_tensor(ids).to(device=self.embeddings.device, dtype=torch.long)
+    return torch.nn.functional.embedding(ids, self.embeddings)
+
+
+def get_embedding(vocab_size=1024, n_dims=256):
+  """Get a real-valued embedding from an integer."""
+  return Embedding(input_dim=vocab_size, output_dim=n_dims)
 
 
 # ---------------- Stacks ------------------------------------------------------
