@@ -202,6 +202,13 @@ NORM_SIGNATURES = {
     'ddsp_group_norm_backward_f32': (c_int, [c_f32p] * 8 + [c_voidp, c_size_t, c_size_t, c_size_t, c_int, c_int, c_voidp]),
 }
 
+# name -> (restype, argtypes) of the entries of csrc/conv_abi.h (training.nn's dilated_conv / Conv2D / DilatedConvStack), typed by
+# conv_entry(): a table of its own for the same reason.
+CONV_SIGNATURES = {
+    'ddsp_dilated_conv_workspace_bytes': (c_size_t, [c_int] * 5),
+    'ddsp_dilated_conv_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t] + [c_int] * 7 + [c_uint, c_voidp]),
+}
+
 # flags (mirror include/ddsp_amd.h)
 HARM_SCALE_EXP_SIGMOID = 0x1
 HARM_NORMALIZE_NYQUIST = 0x2
@@ -243,6 +250,11 @@ GRU_MAX_HIDDEN = 2048                   # units of the GRU (csrc/decoder.hip)
 NOTES_MAX_REGIONS = 1024                # regions whose note-on flags get_note_mask's block keeps in LDS (csrc/notes.hip)
 RESAMPLE_METHODS = {'nearest': 0, 'linear': 1, 'cubic': 2, 'window': 3}
 LOSS_TYPES = {'L1': 0, 'L2': 1, 'COSINE': 2}
+CONVD_RELU_INPUT = 0x1                  # DDSP_CONVD_* of csrc/conv_abi.h
+CONVD_TRANSPOSE_W = 0x2
+CONVD_MASK_OUTPUT = 0x4
+CONVD_MAX_CHANNELS = 1024               # ch_in, ch_out of the dilated convolution (csrc/dilated_conv.hip)
+CONVD_MAX_TAPS = 16
 CONV_ADD_DRY = 0x1
 CONV_MASK_TAP0 = 0x2
 CONV_REVERSE_AUDIO = 0x4
@@ -282,6 +294,8 @@ def load():
     decoder_entry(lib, name)
   for name in NORM_SIGNATURES:
     norm_entry(lib, name)
+  for name in CONV_SIGNATURES:
+    conv_entry(lib, name)
   _lib = lib
   return lib
 
@@ -297,6 +311,13 @@ def norm_entry(lib, name):
   """Entry `name` of NORM_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
   fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/group_norm.hip
   fn.restype, fn.argtypes = NORM_SIGNATURES[name]
+  return fn
+
+
+def conv_entry(lib, name):
+  """Entry `name` of CONV_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
+  fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/dilated_conv.hip
+  fn.restype, fn.argtypes = CONV_SIGNATURES[name]
   return fn
 
 

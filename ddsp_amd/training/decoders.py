@@ -1,9 +1,13 @@
-"""ddsp/training/decoders.py on the MI355X: RnnFcDecoder, the decoder of every shipped model configuration.
+"""ddsp/training/decoders.py on the MI355X: RnnFcDecoder, the decoder of every shipped solo-instrument configuration, and
+DilatedConvDecoder, the synth coder of the MIDI autoencoders (gin/models/midiae/*.gin).
 
-One FcStack per input, a GRU over the concatenated stacks, a further FcStack over (stacks, GRU), a final Dense split into the
-synthesiser controls.  The layers are those of ddsp_amd.training.nn (kernels: csrc/decoder.hip)."""
+RnnFcDecoder: one FcStack per input, a GRU over the concatenated stacks, a further FcStack over (stacks, GRU), a final Dense split
+into the synthesiser controls.  DilatedConvDecoder: a DilatedConvStack over the concatenated inputs, conditioned on z through
+FiLM, then the same final Dense.  The layers are those of ddsp_amd.training.nn (kernels: csrc/decoder.hip, csrc/dilated_conv.hip,
+csrc/group_norm.hip)."""
 import torch
 
+from ddsp_amd import core
 from ddsp_amd.training import nn
 
 
@@ -68,3 +72,71 @@ class RnnFcDecoder(nn.DictLayer):
     if self.stateless:
       output_dict['state'] = new_state
     return output_dict
+
+
+class DilatedConvDecoder(nn.OutputSplitsLayer):
+  """WaveNet style 1-D dilated convolution with optional conditioning (ddsp/training/decoders.py:221-285)."""
+
+  def __init__(self,
+               ch=256,
+               kernel_size=3,
+               layers_per_stack=5,
+               stacks=2,
+               dilation=2,
+               norm_type='layer',
+               resample_stride=1,
+               stacks_per_resample=1,
+               resample_after_convolve=True,
+               input_keys=('ld_scaled', 'f0_scaled'),
+               output_splits=(('amps', 1), ('harmonic_distribution', 60)),
+               conditioning_keys=('z'),
+               precondition_stack=None,
+               spectral_norm=False,
+               ortho_init=False,
+               **kwargs):
+    """Constructor, combines input_keys and conditioning_keys.  The default conditioning_keys is the STRING 'z', as in the
+    reference: list('z') == ['z'].  spectral_norm=True is not built (ValueError)."""
+    self.conditioning_keys = ([] if conditioning_keys is None else
+                              list(conditioning_keys))
+    input_keys = list(input_keys) + self.conditioning_keys
+    super().__init__(input_keys, output_splits, **kwargs)
+
+    # Conditioning.
+    self.n_conditioning = len(self.conditioning_keys)
+    self.conditional = bool(self.conditioning_keys)
+    if not self.conditional and precondition_stack is not None:
+      raise ValueError('You must specify conditioning keys if you specify'
+                       'a precondition stack.')
+
+    # Layers.
+    self.precondition_stack = precondition_stack
+    self.dilated_conv_stack = nn.DilatedConvStack(
+        ch=ch,
+        kernel_size=kernel_size,
+        layers_per_stack=layers_per_stack,
+        stacks=stacks,
+        dilation=dilation,
+        norm_type=norm_type,
+        resample_type='upsample' if resample_stride > 1 else None,
+        resample_stride=resample_stride,
+        stacks_per_resample=stacks_per_resample,
+        resample_after_convolve=resample_after_convolve,
+        conditional=self.conditional,
+        spectral_norm=spectral_norm,
+        ortho_init=ortho_init)
+
+  def _parse_inputs(self, inputs):
+    """Split x and z inputs and run preconditioning."""
+    inputs = [core.tf_float32(v) for v in inputs]
+    if self.conditional:
+      x = torch.cat(inputs[:-self.n_conditioning], dim=-1)
+      z = torch.cat(inputs[-self.n_conditioning:], dim=-1)
+      if self.precondition_stack is not None:
+        z = self.precondition_stack(z)
+      return [x, z]
+    else:
+      return torch.cat(inputs, dim=-1)
+
+  def compute_output(self, *inputs):
+    stack_inputs = self._parse_inputs(inputs)
+    return self.dilated_conv_stack(stack_inputs)

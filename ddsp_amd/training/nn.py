@@ -1,5 +1,5 @@
-"""ddsp/training/nn.py on the MI355X: the note pooling (csrc/notes.hip), the layers RnnFcDecoder is made of (csrc/decoder.hip) and
-the normalisations the encoders use (csrc/group_norm.hip).
+"""ddsp/training/nn.py on the MI355X: the note pooling (csrc/notes.hip), the layers RnnFcDecoder is made of (csrc/decoder.hip), the
+normalisations the encoders use (csrc/group_norm.hip) and the dilated convolution stack (csrc/dilated_conv.hip).
 
 NOTE POOLING (ddsp/training/nn.py:357-557): straight_through_int_quantization, get_note_mask, get_note_mask_from_onset,
 get_note_lengths, get_note_moments, pool_over_notes and get_short_note_loss_mask - what MidiAutoencoder and ZMidiAutoencoder pool
@@ -23,13 +23,21 @@ LayerNormalization: gamma, beta, epsilon 1e-3; GRU: kernel [in, 3 H], recurrent_
 reset_after - built on the first call or through build(in_ch), with Keras' initialisers.  The matrix products whose M is
 batch * time are torch.matmul (plumbing); bias + LayerNorm + activation and the recurrence are the kernels of csrc/decoder.hip,
 forward and backward.  There is no CPU fallback: without the built library or a GPU the layers raise DdspLibraryError.
-NOT BUILT (ValueError): rnn_type='lstm', bidir=True; and the rest of the reference's nn.py.
+NOT BUILT (ValueError): rnn_type='lstm', bidir=True.
 
 NORMALISATION (ddsp/training/nn.py:561-611, 1065-1136): normalize_op, Normalize, ConditionalScaleAndShift, ConditionalNorm,
 get_norm, Identity, get_embedding.  normalize_op - instance, layer or group normalisation of a channel-last [batch, h, w, ch]
 tensor, eps 1e-5 - and Normalize's scale and shift run in ONE kernel each way (csrc/group_norm.hip; C ABI csrc/norm_abi.h):
 two-pass moments, nothing activation-sized kept for the backward but x itself, no atomics, the same bits for a batch row alone
-and inside a batch.  The conditional scale and shift and the embedding's gather are framework ops."""
+and inside a batch.  The conditional scale and shift and the embedding's gather are framework ops.
+
+DILATED CONVOLUTIONS (ddsp/training/nn.py:1153-1323): dilated_conv, Conv2D, Conv2DTranspose, DilatedConvStack.  ReLU -> dilated
+1-D convolution with 'same' padding of a channel-last tensor, forward and the gradient in x, is ONE kernel (csrc/dilated_conv.hip;
+C ABI csrc/conv_abi.h): matrix cores with fp16 hi / lo operands when ch_out is a multiple of 16, the vector ALU otherwise; no
+padded copy, no atomics, the same bits for a batch row alone and inside a batch.  The weight gradients are K matrix products of
+the framework.  The strided resamplers, FiLM's multiply-add and the residual add are framework ops.
+NOT BUILT (ValueError): spectral_norm=True; and the rest of the reference's nn.py (the ResNet layers, SpectralNormalization,
+SingleGru)."""
 import inspect
 import math
 
@@ -979,6 +987,420 @@ class RnnSandwich(_Sequential):
 
   def __init__(self, fc_stack_ch=256, fc_stack_layers=2, rnn_ch=512, rnn_type='gru'):
     super().__init__([FcStack(fc_stack_ch, fc_stack_layers), Rnn(rnn_ch, rnn_type), FcStack(fc_stack_ch, fc_stack_layers)])
+
+
+# ------------------ Dilated convolutions --------------------------------------
+_conv_ws = core.Workspace()
+
+
+def _conv_entry(name):
+  return _lib.conv_entry(_lib.load(), name)
+
+
+def same_pad_left(kernel_size, dilation):
+  """Rows of zeros TF's 'same' padding puts in FRONT of a stride-1 convolution: the total is (kernel_size - 1) * dilation and
+  the odd one goes behind (tensorflow/core/framework/kernel_shape_util.cc GetWindowedOutputSizeVerbose: pad_before = total / 2)."""
+  return ((int(kernel_size) - 1) * int(dilation)) // 2
+
+
+def _run_dilated_conv(x, kernel, bias, dilation, pad_left, flags, mask_src=None, addend=None):
+  """One ddsp_dilated_conv_f32 call on contiguous fp32 tensors: x [b, t, ch_in] -> [b, t, ch_out]; kernel [K, ch_in, ch_out], or
+  [K, ch_out, ch_in] with CONVD_TRANSPOSE_W."""
+  b, t, ch_in = x.shape
+  taps = kernel.shape[0]
+  ch_out = kernel.shape[1] if flags & _lib.CONVD_TRANSPOSE_W else kernel.shape[2]
+  y = torch.empty((b, t, ch_out), dtype=torch.float32, device=x.device)
+  if b:
+    ptr = lambda v: None if v is None else v.data_ptr()
+    ws = _conv_ws.get(_conv_entry('ddsp_dilated_conv_workspace_bytes')(b, t, ch_in, ch_out, taps), x.device)
+    rc = _conv_entry('ddsp_dilated_conv_f32')(x.data_ptr(), kernel.data_ptr(), ptr(bias), ptr(addend), ptr(mask_src), y.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), b, t, ch_in, ch_out, taps, dilation, pad_left, flags,
+                                              core._stream())
+    _checked(rc, 'ddsp_dilated_conv_f32')
+  return y
+
+
+class _DilatedConvFunction(torch.autograd.Function):
+  """torch.autograd node of the dilated convolution: (x [b, t, ch_in], kernel [K, ch_in, ch_out], bias [ch_out] or None) ->
+  [b, t, ch_out].  Forward and the gradient in x are C-ABI calls (the same kernel; the adjoint takes the reversed, transposed taps
+  and the mirrored padding, and multiplies by relu'(x) = (x > 0) in its epilogue).  The gradients whose reduction runs over
+  batch * time are the framework's: K matrix products over views of one relu(x), and a column sum.  Kept for the backward: x and
+  the kernel."""
+
+  @staticmethod
+  def forward(ctx, x, kernel, bias, dilation, relu_input):
+    pad_left = same_pad_left(kernel.shape[0], dilation)
+    y = _run_dilated_conv(x, kernel, bias, dilation, pad_left, _lib.CONVD_RELU_INPUT if relu_input else 0)
+    ctx.save_for_backward(x, kernel)
+    ctx.dilation, ctx.relu_input, ctx.has_bias = dilation, relu_input, bias is not None
+    return y
+
+  @staticmethod
+  def backward(ctx, grad_y):
+    x, kernel = ctx.saved_tensors
+    taps, ch_in, ch_out = kernel.shape
+    d, t = ctx.dilation, x.shape[1]
+    pad_left = same_pad_left(taps, d)
+    grad_y = core.tf_float32(grad_y)
+    dx = dk = db = None
+    if ctx.needs_input_grad[0]:
+      flags = _lib.CONVD_TRANSPOSE_W | (_lib.CONVD_MASK_OUTPUT if ctx.relu_input else 0)
+      dx = _run_dilated_conv(grad_y, kernel, None, d, (taps - 1) * d - pad_left, flags, mask_src=x if ctx.relu_input else None)
+    if ctx.needs_input_grad[1]:
+      a = torch.relu(x) if ctx.relu_input else x
+      dk = torch.zeros_like(kernel)
+      for k in range(taps):
+        shift = k * d - pad_left                      # y[t] takes a[t + shift]
+        lo, hi = max(0, -shift), min(t, t - shift)
+        if hi > lo:
+          dk[k] = torch.matmul(a[:, lo + shift:hi + shift].transpose(1, 2), grad_y[:, lo:hi]).sum(0)      # views: nothing is copied
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+      db = grad_y.reshape(-1, ch_out).sum(0)
+    return dx, dk, db, None, None
+
+
+def dilated_conv(x, kernel, bias=None, dilation=1, relu_input=False):
+  """A dilated 1-D convolution over time of a channel-last tensor, TF 'same' padding, stride 1 - tf.keras.layers.Conv2D(ch_out,
+  (K, 1), dilation_rate=(dilation, 1), padding='same') on [batch, time, 1, ch_in] - with an optional ReLU on its input, in one
+  kernel each way (csrc/dilated_conv.hip; C ABI csrc/conv_abi.h):
+
+    y[b, t, co] = bias[co] + sum_k sum_ci act(x[b, t + k * dilation - pad_left, ci]) * kernel[k, ci, co]
+
+  rows outside [0, time) contributing 0 and pad_left = same_pad_left(K, dilation).  ReLU is applied as x is loaded, the bias
+  added as y is written; there is no padded copy and nothing of size [batch, time, K * ch_in].  ch_out in multiples of 16 runs on
+  the matrix cores (fp16 hi / lo operands behind a power-of-two scale per batch row of x), every other width on the vector ALU.
+  The same bits on every run, for a row alone and for any sub-batch.
+
+  Args:
+    x: [batch, time, ch_in] or [batch, time, 1, ch_in], of any layout or dtype.
+    kernel: [K, ch_in, ch_out] or the Keras layout [K, 1, ch_in, ch_out].
+    bias: [ch_out] or None.
+    dilation: The dilation rate, >= 1.
+    relu_input: Apply ReLU to x first (its gradient at 0 is 0, as tf.nn.relu's).
+
+  Returns:
+    [batch, time, ch_out], or [batch, time, 1, ch_out] for a 4-D x.  Differentiable in x, kernel and bias.
+
+  Raises:
+    ValueError: shapes that do not fit, or beyond the limits of the MI355X path - ch_in, ch_out <= 1024, K <= 16,
+      (K - 1) * dilation < 2 ** 31, batch * time * channels < 2 ** 31.  Checked before anything touches the device.
+  """
+  x_shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(torch.as_tensor(x).shape)
+  k_shape = tuple(kernel.shape) if hasattr(kernel, 'shape') else tuple(torch.as_tensor(kernel).shape)
+  is_4d = len(x_shape) == 4
+  if len(x_shape) not in (3, 4) or (is_4d and x_shape[2] != 1):
+    raise ValueError('dilated_conv: x must be [batch, time, ch_in] or [batch, time, 1, ch_in], got {}'.format(x_shape))
+  if len(k_shape) not in (3, 4) or (len(k_shape) == 4 and k_shape[1] != 1):
+    raise ValueError('dilated_conv: kernel must be [K, ch_in, ch_out] or [K, 1, ch_in, ch_out], got {}'.format(k_shape))
+  batch, steps, ch_in = x_shape[0], x_shape[1], x_shape[-1]
+  taps, ch_out = k_shape[0], k_shape[-1]
+  dilation = int(dilation)
+  if k_shape[-2] != ch_in or min(steps, ch_in, ch_out, taps) < 1:
+    raise ValueError('dilated_conv: x {} and kernel {} must agree in ch_in, and time, K and the channels be at least 1'.format(
+        x_shape, k_shape))
+  if bias is not None and tuple(bias.shape) != (ch_out,):
+    raise ValueError('dilated_conv: bias must be [ch_out] = {}, got {}'.format((ch_out,), tuple(bias.shape)))
+  if dilation < 1:
+    raise ValueError('dilated_conv: dilation must be at least 1, got {}'.format(dilation))
+  if max(ch_in, ch_out) > _lib.CONVD_MAX_CHANNELS or taps > _lib.CONVD_MAX_TAPS:
+    raise ValueError('dilated_conv: at most {} channels and {} taps on the MI355X path, got ch_in = {}, ch_out = {}, K = {}'.format(
+        _lib.CONVD_MAX_CHANNELS, _lib.CONVD_MAX_TAPS, ch_in, ch_out, taps))
+  if (taps - 1) * dilation >= 2 ** 31 or batch * steps * max(ch_in, ch_out) >= 2 ** 31:
+    raise ValueError('dilated_conv: (K - 1) * dilation and batch * time * channels must stay below 2 ** 31, got x {}, kernel {}, '
+                     'dilation {}'.format(x_shape, k_shape, dilation))
+  x, kernel = core.tf_float32(x).reshape(batch, steps, ch_in), core.tf_float32(kernel).reshape(taps, ch_in, ch_out)
+  bias = None if bias is None else core.tf_float32(bias)
+  if core._needs_grad(x, kernel, bias):
+    y = _DilatedConvFunction.apply(x, kernel, bias, dilation, bool(relu_input))
+  else:
+    y = _DilatedConvFunction.forward(core._NoCtx(), x, kernel, bias, dilation, bool(relu_input))
+  return y[:, :, None, :] if is_4d else y
+
+
+def _conv_kernel_init(shape, initializer):
+  """A Keras conv kernel [k, 1, a, b]: 'glorot_uniform' with fans k * a and k * b, or 'orthogonal' over the [k * a, b] flattening."""
+  k, _, a, b = shape
+  if initializer == 'glorot_uniform':
+    limit = math.sqrt(6.0 / (k * a + k * b))
+    return torch.empty(shape, dtype=torch.float32).uniform_(-limit, limit)
+  if initializer == 'orthogonal':
+    return torch.nn.init.orthogonal_(torch.empty((k * a, b), dtype=torch.float32)).reshape(shape)
+  raise ValueError("kernel_initializer must be 'glorot_uniform' or 'orthogonal', got {!r}".format(initializer))
+
+
+def _single(value, what):
+  """k of (k, 1), or k itself."""
+  if isinstance(value, (tuple, list)):
+    if len(value) != 2 or value[1] != 1:
+      raise ValueError('{} must be k or (k, 1): the convolutions run over time only, got {!r}'.format(what, value))
+    value = value[0]
+  if int(value) < 1:
+    raise ValueError('{} must be at least 1, got {!r}'.format(what, value))
+  return int(value)
+
+
+class Conv2D(_Lazy):
+  """tf.keras.layers.Conv2D(filters, (k, 1), (s, 1), dilation_rate=(d, 1), padding='same') on [batch, time, 1, ch] (or
+  [batch, time, ch]).  Weights under the Keras names and layouts: kernel [k, 1, in, out] ('glorot_uniform' with fans k * in and
+  k * out, or 'orthogonal' over the [k * in, out] flattening), bias [out] zeros.
+
+  Stride 1 is dilated_conv (one kernel each way).  A stride s > 1 - the stack's downsampler - is framework ops: F.pad and
+  F.conv1d on the permuted tensor, with TF's 'same' rule (tensorflow/core/framework/kernel_shape_util.cc
+  GetWindowedOutputSizeVerbose: out = ceil(T / s), total = max((out - 1) * s + k - T, 0), pad_before = total // 2, the rest
+  behind)."""
+
+  def __init__(self, filters, kernel_size, strides=1, dilation_rate=1, kernel_initializer='glorot_uniform'):
+    super().__init__()
+    self.filters = _single(filters, 'filters')
+    self.kernel_size = _single(kernel_size, 'kernel_size')
+    self.strides = _single(strides, 'strides')
+    self.dilation_rate = _single(dilation_rate, 'dilation_rate')
+    if self.strides > 1 and self.dilation_rate > 1:
+      raise ValueError('Conv2D: strides > 1 and dilation_rate > 1 together are not supported (as in Keras)')
+    if kernel_initializer not in ('glorot_uniform', 'orthogonal'):
+      raise ValueError("kernel_initializer must be 'glorot_uniform' or 'orthogonal', got {!r}".format(kernel_initializer))
+    self.kernel_initializer = kernel_initializer
+
+  def build(self, in_ch):
+    self.kernel = self._param(_conv_kernel_init((self.kernel_size, 1, in_ch, self.filters), self.kernel_initializer))
+    self.bias = self._param(torch.zeros(self.filters))
+    self.built = True
+
+  def forward(self, x, relu_input=False):
+    self._ensure_built(x.shape[-1])
+    if self.strides == 1:
+      return dilated_conv(x, self.kernel, self.bias, self.dilation_rate, relu_input)
+    x = core.tf_float32(x)
+    if relu_input:
+      x = torch.relu(x)
+    n_dims = x.dim()
+    if n_dims not in (3, 4) or (n_dims == 4 and x.shape[2] != 1):
+      raise ValueError('Conv2D: x must be [batch, time, ch] or [batch, time, 1, ch], got {}'.format(tuple(x.shape)))
+    x = x.reshape(x.shape[0], x.shape[1], x.shape[-1])
+    steps, k, s = x.shape[1], self.kernel_size, self.strides
+    total = max((-(-steps // s) - 1) * s + k - steps, 0)
+    x = torch.nn.functional.pad(x.permute(0, 2, 1), (total // 2, total - total // 2))
+    y = torch.nn.functional.conv1d(x, self.kernel[:, 0].permute(2, 1, 0), self.bias, stride=s).permute(0, 2, 1)
+    return ensure_4d(y) if n_dims == 4 else y
+
+
+class Conv2DTranspose(_Lazy):
+  """tf.keras.layers.Conv2DTranspose(filters, (k, 1), (s, 1), padding='same') on [batch, time, 1, ch] (or [batch, time, ch]) -> time
+  * s rows: the stack's upsampler (k = 2 s).  Weights under the Keras names and layouts: kernel [k, 1, out, in], bias [out] zeros.
+
+  It is the transpose of the 'same' convolution of stride s that maps length T * s to T, whose padding in front is
+  pad_before = max((T - 1) * s + k - T * s, 0) // 2 (tensorflow/core/framework/kernel_shape_util.cc GetWindowedOutputSizeVerbose;
+  tensorflow/python/ops/nn_ops.py conv2d_transpose computes the input gradient of that convolution), = s // 2 for k = 2 s:
+  y[j] = full[j + pad_before], j < T * s, with full[j] = sum_i sum_ci x[i, ci] kernel[j - i * s, 0, co, ci].  Framework ops:
+  F.conv_transpose1d on the permuted tensor, then the crop."""
+
+  def __init__(self, filters, kernel_size, strides=1, kernel_initializer='glorot_uniform'):
+    super().__init__()
+    self.filters = _single(filters, 'filters')
+    self.kernel_size = _single(kernel_size, 'kernel_size')
+    self.strides = _single(strides, 'strides')
+    if self.kernel_size < self.strides:
+      raise ValueError('Conv2DTranspose: kernel_size {} must be at least strides {}'.format(self.kernel_size, self.strides))
+    if kernel_initializer not in ('glorot_uniform', 'orthogonal'):
+      raise ValueError("kernel_initializer must be 'glorot_uniform' or 'orthogonal', got {!r}".format(kernel_initializer))
+    self.kernel_initializer = kernel_initializer
+
+  def build(self, in_ch):
+    self.kernel = self._param(_conv_kernel_init((self.kernel_size, 1, self.filters, in_ch), self.kernel_initializer))
+    self.bias = self._param(torch.zeros(self.filters))
+    self.built = True
+
+  def forward(self, x):
+    x = core.tf_float32(x)
+    self._ensure_built(x.shape[-1])
+    n_dims = x.dim()
+    if n_dims not in (3, 4) or (n_dims == 4 and x.shape[2] != 1):
+      raise ValueError('Conv2DTranspose: x must be [batch, time, ch] or [batch, time, 1, ch], got {}'.format(tuple(x.shape)))
+    x = x.reshape(x.shape[0], x.shape[1], x.shape[-1])
+    steps, k, s = x.shape[1], self.kernel_size, self.strides
+    before = max((steps - 1) * s + k - steps * s, 0) // 2
+    full = torch.nn.functional.conv_transpose1d(x.permute(0, 2, 1), self.kernel[:, 0].permute(2, 1, 0), self.bias, stride=s)
+    y = full[:, :, before:before + steps * s].permute(0, 2, 1)
+    return ensure_4d(y) if n_dims == 4 else y
+
+
+class DilatedConvLayer(torch.nn.Module):
+  """The reference's `dilated_conv` Sequential (ddsp/training/nn.py:1226-1237): Activation(relu) -> Conv2D, here one kernel.  The
+  convolution's weights are conv.kernel and conv.bias."""
+
+  def __init__(self, conv):
+    super().__init__()
+    self.conv = conv
+
+  def forward(self, x):
+    return self.conv(x, relu_input=True)
+
+
+class DilatedConvStack(torch.nn.Module):
+  """Stack of dilated 1-D convolutions, optional conditioning at each layer (ddsp/training/nn.py:1153-1323).
+
+  conv_in, then stacks * layers_per_stack residual layers x = x + norm(conv(relu(x))) whose dilation is dilation ** depth inside
+  a stack (a negative `dilation` decreases with depth), with resampling layers between the stacks if asked for.  The
+  convolutions are dilated_conv (ReLU, taps and bias in one kernel each way), the norms Normalize / ConditionalNorm (one kernel
+  each way); FiLM's multiply-add, the residual add and the two resamplers are framework ops.  spectral_norm=True is not built
+  (ValueError)."""
+
+  def __init__(self,
+               ch=256,
+               layers_per_stack=5,
+               stacks=2,
+               kernel_size=3,
+               dilation=2,
+               norm_type=None,
+               resample_type=None,
+               resample_stride=1,
+               stacks_per_resample=1,
+               resample_after_convolve=True,
+               spectral_norm=False,
+               ortho_init=False,
+               shift_only=False,
+               conditional=False,
+               **kwargs):
+    """Constructor.
+
+    Args:
+      ch: Number of channels in each convolution layer.
+      layers_per_stack: Convolution layers in each 'stack'. Dilation increases exponentially with layer depth inside a stack.
+      stacks: Number of convolutions stacks.
+      kernel_size: Size of convolution kernel.
+      dilation: Exponent base of dilation factor within a stack.
+      norm_type: Type of normalization before each nonlinearity, choose from 'layer', 'instance', or 'group'.
+      resample_type: Whether to 'upsample' or 'downsample' the signal. None performs no resampling.
+      resample_stride: Stride for upsample or downsample layers.
+      stacks_per_resample: Number of stacks per a resample layer.
+      resample_after_convolve: Ordering of convolution and resampling. If True, apply `stacks_per_resample` stacks of
+        convolution then a resampling layer. If False, apply the opposite order.
+      spectral_norm: Not built on the MI355X path (ValueError if True).
+      ortho_init: Orthogonally initialize the kernel weights.
+      shift_only: Learn/condition only shifts of normalization and not scale.
+      conditional: Use conditioning signal to modulate shifts (and scales) of normalization (FiLM), instead of learned
+        parameters.
+      **kwargs: name.
+
+    Returns:
+      Convolved and resampled signal. If inputs shape is [batch, time, ch_in], output shape is [batch, time_out, ch], where `ch`
+      is the class kwarg, and `time_out` is resample_stride ** (stacks // stacks_per_resample) times smaller or larger than
+      `time` depending on whether `resample_type` is upsampling or downsampling.
+    """
+    name = kwargs.pop('name', None)
+    if kwargs:
+      raise TypeError('DilatedConvStack: unknown arguments {}'.format(sorted(kwargs)))
+    if spectral_norm:
+      raise ValueError('spectral_norm=True is not built on the MI355X path')
+    super().__init__()
+    self.name = name
+    self.conditional = conditional
+    self.norm_type = norm_type
+    self.resample_after_convolve = resample_after_convolve
+
+    initializer = 'orthogonal' if ortho_init else 'glorot_uniform'
+
+    def conv(ch, k, stride=1, dilation=1, transpose=False):
+      """Make a convolution layer."""
+      if transpose:
+        return Conv2DTranspose(ch, (k, 1), (stride, 1), kernel_initializer=initializer)
+      return Conv2D(ch, (k, 1), (stride, 1), dilation_rate=(dilation, 1), kernel_initializer=initializer)
+
+    # Layer Factories.
+    def dilated_conv_layer(i):
+      """Generates a dilated convolution layer, based on `i` depth in stack."""
+      if dilation > 0:
+        dilation_rate = int(dilation ** i)
+      else:
+        # If dilation is negative, decrease dilation with depth instead of increasing.
+        dilation_rate = int((-dilation) ** (layers_per_stack - i - 1))
+      return DilatedConvLayer(conv(ch, kernel_size, 1, dilation_rate))
+
+    def resample_layer():
+      """Generates a resampling layer."""
+      if resample_type == 'downsample':
+        return conv(ch, resample_stride, resample_stride)
+      elif resample_type == 'upsample':
+        return conv(ch, resample_stride * 2, resample_stride, transpose=True)
+      else:
+        raise ValueError(f'invalid resample type: {resample_type}, '
+                         'must be either `upsample` or `downsample`.')
+
+    # Layers.
+    self.conv_in = conv(ch, kernel_size)
+    self.layers = torch.nn.ModuleList()
+    self.norms = torch.nn.ModuleList()
+    self.resample_layers = torch.nn.ModuleList()
+
+    # Stacks.
+    for i in range(stacks):
+      # Option: Resample before convolve.
+      if (resample_type and not self.resample_after_convolve and
+          i % stacks_per_resample == 0):
+        self.resample_layers.append(resample_layer())
+
+      # Convolve.
+      for j in range(layers_per_stack):
+        # Convolution.
+        layer = dilated_conv_layer(j)
+        # Normalization / scale and shift.
+        if self.conditional:
+          norm = ConditionalNorm(norm_type=norm_type, shift_only=shift_only)
+        else:
+          norm = Normalize(norm_type=norm_type)
+
+        # Add to the stack.
+        self.layers.append(layer)
+        self.norms.append(norm)
+
+      # Option: Resample after convolve.
+      if (resample_type and self.resample_after_convolve and
+          (i + 1) % stacks_per_resample == 0):
+        self.resample_layers.append(resample_layer())
+
+    # For forward pass, calculate layers per a resample.
+    if len(self.resample_layers):
+      self.layers_per_resample = len(self.layers) // len(self.resample_layers)
+    else:
+      self.layers_per_resample = 0
+
+  def forward(self, inputs):
+    """Forward pass: x [batch, time, ch_in] (or 4-D), or the pair (x, z) when conditional -> [batch, time_out, ch]."""
+    # Get inputs.
+    if self.conditional:
+      x, z = inputs
+      x = ensure_4d(core.tf_float32(x))
+      z = ensure_4d(core.tf_float32(z))
+    else:
+      x = inputs
+      x = ensure_4d(core.tf_float32(x))
+
+    # Run them through the network.
+    x = self.conv_in(x)
+
+    # Stacks.
+    for i, (layer, norm) in enumerate(zip(self.layers, self.norms)):
+
+      # Optional: Resample before conv.
+      if (len(self.resample_layers) and not self.resample_after_convolve and
+          i % self.layers_per_resample == 0):
+        x = self.resample_layers[i // self.layers_per_resample](x)
+
+      # Scale and shift by conditioning.
+      if self.conditional:
+        y = layer(x)
+        x = x + norm([y, z])
+
+      # Regular residual network.
+      else:
+        x = x + norm(layer(x))
+
+      # Optional: Resample after conv.
+      if (len(self.resample_layers) and self.resample_after_convolve and
+          (i + 1) % self.layers_per_resample == 0):
+        x = self.resample_layers[i // self.layers_per_resample](x)
+
+    return x[:, :, 0, :]  # Convert back to 3-D.
 
 
 class FcStackOut(torch.nn.Module):
