@@ -67,6 +67,11 @@ def _stream_of(device):
   return torch._C._cuda_getCurrentRawStream(index)
 
 
+# Whether torch's current stream is being captured into a graph: the one predicate Workspace asks, for CUDA devices only (it
+# asks the GPU runtime, which a machine without a GPU does not have).  The C call itself, for the reason _stream gives.
+_capturing = torch._C._cuda_isCurrentStreamCapturing
+
+
 def require_no_grad(op, *tensors):
   """The raw kernel wrappers return tensors without a grad_fn.  Where no torch.autograd node covers an op, an input
   that requires grad must fail loudly instead of silently cutting the graph (a branch summed through Add would just
@@ -99,21 +104,30 @@ class Workspace:
   allocator hands a freed block back to the stream it was allocated on).  A Processor instance may therefore be
   called from several streams; each stream pays for its own scratch.  The stream is the current one of the tensor's
   device, which is the current device (tf_float32 refuses tensors of another GPU: kernels launch on the current one); at most `kMaxStreams` buffers are kept, least recently used first out (short-lived streams do not pile up
-  scratch, and a recycled stream handle finds a buffer that was last used on that very handle)."""
+  scratch, and a recycled stream handle finds a buffer that was last used on that very handle).
+
+  A captured graph holds the scratch pointer as a kernel argument, and it usually is the pointer of a buffer made during
+  the warm-up on the capture stream, outside the graph's own pool.  A buffer handed out while the current stream is
+  capturing is therefore kept for as long as this Workspace lives: neither growth nor the eviction above frees it, so
+  every replay finds its scratch.  Buffers handed out only outside a capture are replaced and evicted as before."""
   kMaxStreams = 8
 
   def __init__(self):
     self._bufs = {}            # insertion order = recency (a hit is re-inserted)
+    self._captured = {}        # id -> buffer a capture was handed: never freed while self lives
 
   def get(self, nbytes, device):
     nbytes = max(int(nbytes), 16)
-    key = (device, _stream_of(device) if device.type == 'cuda' else None)
+    stream = _stream_of(device) if device.type == 'cuda' else None
+    key = (device, stream)
     buf = self._bufs.pop(key, None)
     if buf is None or buf.numel() < nbytes:
       buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
     self._bufs[key] = buf
     while len(self._bufs) > self.kMaxStreams:
       self._bufs.pop(next(iter(self._bufs)))
+    if stream and _capturing():            # (handle 0, the null stream, cannot be captured: the eager default pays no query)
+      self._captured[id(buf)] = buf
     return buf
 
 

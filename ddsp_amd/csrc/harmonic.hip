@@ -1568,8 +1568,7 @@ extern "C" int ddsp_harmonic_signal_tf_order_f32(const float* ctl_amp, const flo
   if (!amp_linear && (N % F != 0)) return DDSP_ERR_BAD_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int kblocks = (K + 63) / 64;
-  if (kblocks > 1 && hipMemsetAsync(audio, 0, (size_t)B * N * sizeof(float), st) != hipSuccess)
-    return DDSP_ERR_LAUNCH;
+  if (kblocks > 1) zero_f32_async(audio, (size_t)B * N, st);     // (a kernel, not a memset node: launch.h says why)
   hipLaunchKernelGGL(harm_tf_order_kernel, dim3(kblocks, B), dim3(64), 0, st, ctl_amp, ctl_hd, f0_hz,
                      audio, F, K, N, amp_linear ? 1 : N / F, (float)sample_rate,
                      (float)(sample_rate / 2.0), amp_linear, (flags & DDSP_HARM_ANGULAR_CUMSUM) ? 1 : 0);

@@ -507,7 +507,7 @@ static int sl_backward_impl(const float* target_audio, const float* audio, const
                                             ddsp_spectral_loss_grad_workspace_bytes(B, N, fft_sizes, n_sizes))) return rc;
     slab = (float*)grad_workspace;
   } else                                                         // (the gather writes every sample once: nothing to clear)
-  if (hipMemsetAsync(grad_audio, 0, (size_t)B * N * sizeof(float), st) != hipSuccess) return DDSP_ERR_LAUNCH;
+    zero_f32_async(grad_audio, (size_t)B * N, st);               // (a kernel, not a memset node: launch.h says why)
   SlFinishArgs fin;
   fin.n_sizes = n_sizes; fin.mag_weight = mag_weight; fin.logmag_weight = logmag_weight;
   int offset = 0;

@@ -248,6 +248,9 @@ ROWS += [
         [U('amplitudes', B, FR, 1, grad=False), U('harmonic_distribution', B, FR, K, grad=False), U('f0_hz', B, FR, 1, lo=180.0, hi=260.0, grad=False)]),
     Row('core.harmonic_synthesis/tf_op_order', lambda d, f, a, h: d.core.harmonic_synthesis(f, a, harmonic_distribution=h, n_samples=NS, tf_op_order=True),
         [U('frequencies', B, FR, 1, lo=180.0, hi=260.0, grad=False), U('amplitudes', B, FR, 1, grad=False), U('harmonic_distribution', B, FR, K, grad=False)]),
+    # 72 harmonics: two blocks of 64 add into an audio buffer the entry clears first (two addends: the order cannot show)
+    Row('core.harmonic_synthesis/tf_op_order_k72', lambda d, f, a, h: d.core.harmonic_synthesis(f, a, harmonic_distribution=h, n_samples=NS, tf_op_order=True),
+        [U('frequencies', B, FR, 1, lo=60.0, hi=100.0, grad=False), U('amplitudes', B, FR, 1, grad=False), U('harmonic_distribution', B, FR, 72, grad=False)]),
     Row('core.harmonic_oscillator_bank', lambda d, f, a: d.core.harmonic_oscillator_bank(f, a),
         [U('frequency', B, 320, 1, lo=180.0, hi=260.0, grad=False), U('amplitude_envelopes', B, 320, K, grad=False)]),
     Row('FilteredNoise.get_controls', lambda d, m: d.synths.FilteredNoise(n_samples=NS).get_controls(m), [N('magnitudes', B, FR, 64, grad=False)]),
