@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "split_f16.h"      // f32x4
+#include "nan_select.h"     // relu_keep_nan, max_keep_nan, min_keep_nan
 
 namespace ddsp {
 
@@ -77,6 +78,29 @@ __device__ __forceinline__ int pow2_exponent(float m) {
   int e = field - 126;
   if (m == 0.0f || field == 255) e = 0;
   return e < -125 ? -125 : (e > 126 ? 126 : e);
+}
+// float -> int32 as gfx950's conversion instructions give it (v_cvt_i32_f32, v_cvt_flr_i32_f32; the ISA manual's rule for every
+// float-to-integer conversion): NaN -> 0, a value beyond the int range - the infinities included - saturates.  On the device a
+// plain cast already IS that instruction.  This spells the rule out for host builds of the kernels (the CPU emulation of tests/):
+// there a cast of any of these gives INT_MIN, and an index made from it lies 8 GiB from where the device's would.
+__device__ __forceinline__ int cvt_i32_saturating(float x) {
+#if defined(__AMDGCN__)
+  return (int)x;                                   // v_cvt_i32_f32
+#endif
+  if (x != x) return 0;
+  if (x >= 2147483648.0f) return 0x7fffffff;
+  if (x <= -2147483648.0f) return (int)0x80000000u;
+  return (int)x;
+}
+// (int)floor(x) in one instruction (harmonic_table.hip's phase B); tests/test_nonfinite_table.py pins the host branch
+__device__ __forceinline__ int wt_floor_int(float x) {
+#if defined(__AMDGCN__)
+  int r;
+  __asm__("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+#else
+  return cvt_i32_saturating(floorf(x));
+#endif
 }
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_mov0(double v) {

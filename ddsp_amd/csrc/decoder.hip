@@ -50,7 +50,7 @@ __device__ __forceinline__ float sigmoidf_(float a) { return 1.0f / (1.0f + expf
 __device__ __forceinline__ float act_fwd(float u, int act) {
   switch (act) {
     case DDSP_ACT_LEAKY_RELU: return u > 0.0f ? u : 0.2f * u;
-    case DDSP_ACT_RELU: return u > 0.0f ? u : 0.0f;
+    case DDSP_ACT_RELU: return relu_keep_nan(u);
     case DDSP_ACT_SIGMOID: return sigmoidf_(u);
     case DDSP_ACT_TANH: return tanhf(u);
     default: return u;

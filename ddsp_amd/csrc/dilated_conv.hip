@@ -95,7 +95,10 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict_
 __device__ __forceinline__ float epilogue(float sum, size_t at, int co, const float* __restrict__ bias, const float* __restrict__ addend,
                                           const float* __restrict__ mask_src) {
   if (bias) sum += bias[co];
-  if (mask_src) sum = mask_src[at] > 0.0f ? sum : 0.0f;
+  if (mask_src) {                                        // relu'(x): 1 above 0, 0 at and below; where x is a NaN the gradient is one too
+    const float m = mask_src[at];
+    sum = m > 0.0f ? sum : (m != m ? m : 0.0f);
+  }
   if (addend) sum += addend[at];
   return sum;
 }
@@ -171,7 +174,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict_
     }
     float v[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = ldexpf(relu ? fmaxf(v_next[q], 0.0f) : v_next[q], -e_x);
+    for (int q = 0; q < 8; ++q) v[q] = ldexpf(relu ? relu_keep_nan(v_next[q]) : v_next[q], -e_x);
     f16x8 a_hi, a_lo;
     split8(v, a_hi, a_lo);
     __syncthreads();
@@ -219,7 +222,7 @@ __global__ __launch_bounds__(256) void conv_plain_kernel(const float* __restrict
     if (s < 0 || s >= T) continue;
     const float* xr = x + (b * (size_t)T + (size_t)s) * Cin;
     for (int ci = 0; ci < Cin; ++ci) {
-      const float a = relu ? fmaxf(xr[ci], 0.0f) : xr[ci];
+      const float a = relu ? relu_keep_nan(xr[ci]) : xr[ci];
       sum = fmaf(a, tap_weight(w, k, ci, co, Cin, Cout, K, transposed), sum);
     }
   }

@@ -26,8 +26,8 @@ constexpr int kFramesPerBlock = kThreads / kWave;
 constexpr float kLn10 = 2.302585092994046f;
 
 __device__ __forceinline__ float power_to_db(float power, float pmin, float ref_db, float range_db) {
-  const float db = 10.0f * (logf(fmaxf(pmin, power)) / kLn10) - ref_db;       // core.log10: log(x) / log(10)
-  return fmaxf(db, -range_db);
+  const float db = 10.0f * (logf(max_keep_nan(power, pmin)) / kLn10) - ref_db;       // core.log10: log(x) / log(10)
+  return max_keep_nan(db, -range_db);
 }
 
 struct EnergyArgs { long rows; int N, n_frames, frame_size, hop, pad_left, db; float inv_size, pmin, ref_db, range_db; };

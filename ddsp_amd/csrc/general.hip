@@ -908,7 +908,10 @@ __global__ __launch_bounds__(kThreads) void harmonic_frequencies_kernel(const fl
 // core.remove_above_nyquist (ddsp/core.py:869-891)
 __global__ __launch_bounds__(kThreads) void remove_above_nyquist_kernel(const float* __restrict__ freq, const float* __restrict__ amp,
                                                                         float* __restrict__ out, size_t n, float nyquist) {
-  for (size_t i = global_thread(); i < n; i += grid_threads()) out[i] = freq[i] >= nyquist ? 0.0f : amp[i];
+  for (size_t i = global_thread(); i < n; i += grid_threads()) {
+    const float f = freq[i];
+    out[i] = f >= nyquist ? 0.0f : (f != f ? f : amp[i]);      // a NaN frequency is above nothing and below nothing: it stays a NaN
+  }
 }
 // core.angular_cumsum (ddsp/core.py:800-866) on [B, T, C]: the phase in [0, 2 pi).  fp64 revolutions, chunks of 256 samples:
 // sums per chunk, an exclusive wrapped prefix over the chunks, then the running phase inside each chunk - exact to ~1e-13

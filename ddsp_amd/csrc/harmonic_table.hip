@@ -282,16 +282,8 @@ __device__ __forceinline__ h16x2 wt_rest_halves(f32x2 c2048, h16x2 h) {
   return (h16x2){(__fp16)fmaf((float)h[0], -kLoScale, c2048[0]), (__fp16)fmaf((float)h[1], -kLoScale, c2048[1])};
 #endif
 }
-// (int)floor(x) in one instruction
-__device__ __forceinline__ int wt_floor_int(float x) {
-#if defined(__AMDGCN__)
-  int r;
-  __asm__("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-#else
-  return (int)floorf(x);
-#endif
-}
+// (wt_floor_int, (int)floor(x) in one instruction, is common.h's: phase B adds it to an LDS address, and a NaN f0_hz arrives there
+// as a NaN position)
 // (a0 b1 + c0, a1 b0 + c1): the halves of b swapped
 __device__ __forceinline__ f32x2 wt_pk_fma_swap(f32x2 a, f32x2 b, f32x2 c) {
   return (f32x2){fmaf(a[0], b[1], c[0]), fmaf(a[1], b[0], c[1])};

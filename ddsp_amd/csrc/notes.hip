@@ -84,7 +84,7 @@ __device__ __forceinline__ void block_scan(int& cnt, int& flag, double& seg, int
 // does step p of the row start a region?  (p < T)
 __device__ __forceinline__ int edge_at(const float* q, const float* onset, int p, int T) {
   if (p == 0) return 1;
-  if (onset) return (int)onset[p];                       // truncation, as tf.cast
+  if (onset) return cvt_i32_saturating(onset[p]);        // truncation, as tf.cast (a NaN: 0; the counts it enters are range-checked)
   return (p < T - 1 && q[p] != q[p - 1]) ? 1 : 0;        // |diff| > 0; the last step never starts a region
 }
 

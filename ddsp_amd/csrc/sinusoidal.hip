@@ -35,6 +35,7 @@
 #include "../../include/ddsp_amd.h"
 #include "profile.h"
 #include "launch.h"
+#include "nan_select.h"
 
 namespace ddsp {
 namespace sinusoidal {
@@ -190,10 +191,10 @@ __global__ __launch_bounds__(kThreads) void unit_convert_kernel(const float* __r
     case DDSP_CONVERT_MIDI_TO_HZ_ZERO_SILENCE: y = (x == 0.0f) ? 0.0f : midi_to_hz(x); break;
     case DDSP_CONVERT_HZ_TO_MIDI: y = (x <= 0.0f) ? 0.0f : 12.0f * (log2f(x) - log2f(440.0f)) + 69.0f; break;
     case DDSP_CONVERT_UNIT_TO_MIDI: y = p0 + (p1 - p0) * x; break;
-    case DDSP_CONVERT_UNIT_TO_MIDI_CLIP: y = p0 + (p1 - p0) * fminf(fmaxf(x, 0.0f), 1.0f); break;
+    case DDSP_CONVERT_UNIT_TO_MIDI_CLIP: y = p0 + (p1 - p0) * min_keep_nan(max_keep_nan(x, 0.0f), 1.0f); break;
     case DDSP_CONVERT_MIDI_TO_UNIT: y = (x - p0) / (p1 - p0); break;
-    case DDSP_CONVERT_MIDI_TO_UNIT_CLIP: y = fminf(fmaxf((x - p0) / (p1 - p0), 0.0f), 1.0f); break;
-    case DDSP_CONVERT_LOG_FLOOR: { const float m = fmaxf(p1, x); y = logf(m <= 0.0f ? 1e-5f : m) / p0; break; }   // core.log10(tf.maximum(amin, x)): p0 = ln 10, p1 = amin
+    case DDSP_CONVERT_MIDI_TO_UNIT_CLIP: y = min_keep_nan(max_keep_nan((x - p0) / (p1 - p0), 0.0f), 1.0f); break;
+    case DDSP_CONVERT_LOG_FLOOR: { const float m = max_keep_nan(x, p1); y = logf(m <= 0.0f ? 1e-5f : m) / p0; break; }   // core.log10(tf.maximum(amin, x)): p0 = ln 10, p1 = amin
     default: y = logf(x <= 0.0f ? p1 : x) / p0; break;                  // DDSP_CONVERT_LOGB: p0 = safe log of the base, p1 = eps
   }
   out[i] = y;

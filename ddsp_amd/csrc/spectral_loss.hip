@@ -249,8 +249,8 @@ __global__ __launch_bounds__(256) void loudness_from_mag_kernel(const float* __r
   float acc = 0.0f;
   for (int k = lane; k < p.bins; k += 64) acc = fmaf(wt[k] * m[k], m[k], acc);
   const float power = wave_sum(acc) / (float)p.bins;
-  const float db = 10.0f * (__logf(fmaxf(p.pmin, power)) * 0.4342944819032518f) - p.ref_db;
-  if (lane == 0) loud[row] = fmaxf(db, -p.range_db);
+  const float db = 10.0f * (__logf(max_keep_nan(power, p.pmin)) * 0.4342944819032518f) - p.ref_db;
+  if (lane == 0) loud[row] = max_keep_nan(db, -p.range_db);
 }
 
 // grad_mag[b, f, k] = dL/d loudness[b, f] * d loudness / d |X_k|: 10 / (ln 10 P) * 2 w_k |X_k| / bins, nothing where a max() clips
@@ -264,9 +264,9 @@ __global__ __launch_bounds__(256) void loudness_from_mag_bwd_kernel(const float*
   float acc = 0.0f;
   for (int k = lane; k < p.bins; k += 64) acc = fmaf(wt[k] * m[k], m[k], acc);
   const float power = wave_sum(acc) / (float)p.bins;
-  const float db = 10.0f * (__logf(fmaxf(p.pmin, power)) * 0.4342944819032518f) - p.ref_db;
-  const bool live = power > p.pmin && db > -p.range_db;
-  const float gp = live ? grad_loud[row] * (10.0f * 0.4342944819032518f) / power * (2.0f / (float)p.bins) : 0.0f;
+  const float db = 10.0f * (__logf(max_keep_nan(power, p.pmin)) * 0.4342944819032518f) - p.ref_db;
+  const bool clipped = power <= p.pmin || db <= -p.range_db;       // (a NaN power is not clipped: its gradient is a NaN)
+  const float gp = clipped ? 0.0f : grad_loud[row] * (10.0f * 0.4342944819032518f) / power * (2.0f / (float)p.bins);
   float* __restrict__ gm = grad_mag + row * p.bins;
   for (int k = lane; k < p.bins; k += 64) gm[k] = gp * wt[k] * m[k];
 }

@@ -570,7 +570,7 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
     auto bin_grad = [&](float2 xt, float2 xa, bool count, int bin) {
       if constexpr (COT) {
         const float ma = sl_sqrt(fmaf(xa.x, xa.x, xa.y * xa.y));
-        if (!(ma > 0.0f)) return make_float2(0.f, 0.f);           // |z| has gradient 0 at z = 0 (tf.abs)
+        if (ma <= 0.0f) return make_float2(0.f, 0.f);             // |z| has gradient 0 at z = 0 (tf.abs); a NaN |z| is no zero
         const float coef = cot[((size_t)b * n_frames + f0 + g) * (H + 1) + bin] * __builtin_amdgcn_rcpf(ma);
         return make_float2(coef * xa.x, coef * xa.y);
       }
@@ -579,7 +579,7 @@ __device__ __forceinline__ void stft_l1_bwd_block(float2* s, double (*red)[kSlTh
         dm_sum += fabsf(mt - ma);
         dl_sum += fabsf(sl_log2(mt <= 0.0f ? safe_eps : mt) - sl_log2(ma <= 0.0f ? safe_eps : ma));
       }
-      if (!(ma > 0.0f)) return make_float2(0.f, 0.f);
+      if (ma <= 0.0f) return make_float2(0.f, 0.f);
       const float dmag = mt - ma;
       const float dlog = sl_log2(mt <= 0.0f ? safe_eps : mt) - sl_log2(ma);
       const float sm = dmag > 0.0f ? 1.0f : (dmag < 0.0f ? -1.0f : 0.0f);
@@ -821,7 +821,7 @@ __device__ __forceinline__ void stft_l1_big_block(float2* s, double (*red)[kSlTh
       dm_sum += fabsf(mt - ma);
       dl_sum += fabsf(lt - la);
     }
-    if (!BWD || !(ma > 0.0f)) return make_float2(0.f, 0.f);
+    if (!BWD || ma <= 0.0f) return make_float2(0.f, 0.f);
     const float dmag = mt - ma, dlog = lt - la;
     const float sm = dmag > 0.0f ? 1.0f : (dmag < 0.0f ? -1.0f : 0.0f);
     const float sl = dlog > 0.0f ? 1.0f : (dlog < 0.0f ? -1.0f : 0.0f);
@@ -955,7 +955,7 @@ __global__ __launch_bounds__(kSlThreads) void stft_tq_cot_bwd_kernel(const float
     const float* __restrict__ crow = cot + ((size_t)b * n_frames + f0 + g) * (H + 1);
     auto bin_grad = [&](float2 xa, int bin) {                                 // dL/dX: cot * X / |X| (0 at X = 0: tf.abs)
       const float ma = sl_sqrt(fmaf(xa.x, xa.x, xa.y * xa.y));
-      if (!(ma > 0.0f)) return make_float2(0.f, 0.f);
+      if (ma <= 0.0f) return make_float2(0.f, 0.f);
       const float coef = crow[bin] * __builtin_amdgcn_rcpf(ma);
       return make_float2(coef * xa.x, coef * xa.y);
     };

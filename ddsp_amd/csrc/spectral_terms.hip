@@ -40,7 +40,7 @@ __device__ __forceinline__ float st_weight(const float* __restrict__ wts, const 
   return wts[i];
 }
 __device__ __forceinline__ float st_safe_log(float x, float eps) { return __logf(x <= 0.0f ? eps : x); }
-__device__ __forceinline__ float st_sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+__device__ __forceinline__ float st_sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : (x != x ? x : 0.0f)); }   // tf.sign: a NaN stays one
 
 // inclusive scan over the 64 lanes, ascending (up) or descending (down) lane order
 __device__ __forceinline__ float st_scan_up(float x, int lane) {
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(64 * kStRowsPerBlock) void spec_terms_grad_kernel(c
       const float t = t0[k], v = v0[k];
       const float w = st_weight(wts, p, b, f, k);
       if (c_mag != 0.0f) g_total += c_mag * st_g(lt, t, v, w, w_row);
-      if (c_log != 0.0f && v > 0.0f)                                                 // safe_log passes a gradient where v > 0
+      if (c_log != 0.0f && !(v <= 0.0f))                                             // safe_log passes a gradient where v > 0 (and a NaN where v is one)
         g_total += c_log * st_g(lt, st_safe_log(t, p.safe_eps), __logf(v), w, w_row) / v;
       if (c_dt != 0.0f) {
         // b_dt[f, k] = v[f+1, k] - v[f, k]:  d/dv[f, k] = -G(f, k) + G(f-1, k)

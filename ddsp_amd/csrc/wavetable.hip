@@ -247,8 +247,10 @@ __global__ __launch_bounds__(kThreads) void wt_sample_kernel(const float* __rest
 __device__ __forceinline__ void split_position(float phase, int L, int& i0, float& frac) {
   const float fl_L = (float)L;
   const float hi = rn_mul(phase, fl_L);
-  if (!(hi > -2.0f)) { i0 = -3; frac = 0.0f; return; }
-  if (hi > fl_L + 2.0f) { i0 = L + 2; frac = 0.0f; return; }
+  // (a NaN or infinite position has no table entry either, and its fraction is a NaN - hi - hi, 0 for every finite hi -: the
+  // lerp of the two missing points is then a NaN and not a 0)
+  if (!(hi > -2.0f)) { i0 = -3; frac = hi - hi; return; }
+  if (hi > fl_L + 2.0f) { i0 = L + 2; frac = hi - hi; return; }
   const float lo = fmaf(phase, fl_L, -hi);
   const float fl = floorf(hi);
   i0 = (int)fl;

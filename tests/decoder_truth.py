@@ -15,8 +15,8 @@ import torch
 EPSILON = 1e-3
 ACTIVATIONS = {
     'leaky_relu': lambda x: torch.where(x > 0, x, 0.2 * x),
-    'relu': lambda x: torch.where(x > 0, x, torch.zeros_like(x)),
-    'sigmoid': lambda x: 1.0 / (1.0 + torch.exp(-x)),
+    'relu': torch.relu,                    # (gradient 0 at 0 as tf.nn.relu's; a NaN stays a NaN, which torch.where(x > 0, x, 0) loses)
+    'sigmoid': torch.sigmoid,              # (tf.sigmoid: gradient y (1 - y), 0 at -Inf where 1 / (1 + exp(-x)) differentiates to 0 * Inf)
     'tanh': torch.tanh,
     'linear': lambda x: x,
 }
@@ -61,8 +61,8 @@ def gru_recurrence(mx, recurrent_kernel, recurrent_bias, h0=None, dtype=torch.fl
   out = []
   for t in range(mx.shape[1]):
     mh = torch.matmul(h, rk) + rb
-    z = 1.0 / (1.0 + torch.exp(-(mx[:, t, :hidden] + mh[:, :hidden])))
-    r = 1.0 / (1.0 + torch.exp(-(mx[:, t, hidden:2 * hidden] + mh[:, hidden:2 * hidden])))
+    z = torch.sigmoid(mx[:, t, :hidden] + mh[:, :hidden])
+    r = torch.sigmoid(mx[:, t, hidden:2 * hidden] + mh[:, hidden:2 * hidden])
     hh = torch.tanh(mx[:, t, 2 * hidden:] + r * mh[:, 2 * hidden:])
     h = z * h + (1.0 - z) * hh
     out.append(h)

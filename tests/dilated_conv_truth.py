@@ -52,7 +52,7 @@ def conv(x, kernel, bias=None, dilation=1, relu_input=False, dtype=torch.float64
   x, is_4d = _3d(x, dtype)
   kernel = _kernel(kernel, dtype)
   if relu_input:
-    x = torch.where(x > 0, x, torch.zeros_like(x))               # gradient 0 at x = 0, as tf.nn.relu's
+    x = torch.relu(x)                                            # gradient 0 at x = 0 and a NaN kept, as tf.nn.relu's
   steps, taps = x.shape[1], kernel.shape[0]
   pad_left = same_pad_left(taps, dilation)
   y = x.new_zeros((x.shape[0], steps, kernel.shape[2]))
