@@ -209,6 +209,13 @@ CONV_SIGNATURES = {
     'ddsp_dilated_conv_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t] + [c_int] * 7 + [c_uint, c_voidp]),
 }
 
+# name -> (restype, argtypes) of the entries of csrc/conv2d_abi.h (training.nn's conv2d / SpatialConv2D / ResNet), typed by
+# conv2d_entry(): a table of its own for the same reason.
+CONV2D_SIGNATURES = {
+    'ddsp_conv2d_workspace_bytes': (c_size_t, [c_int] * 9 + [c_uint]),
+    'ddsp_conv2d_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t] + [c_int] * 9 + [c_uint, c_voidp]),
+}
+
 # flags (mirror include/ddsp_amd.h)
 HARM_SCALE_EXP_SIGMOID = 0x1
 HARM_NORMALIZE_NYQUIST = 0x2
@@ -255,6 +262,13 @@ CONVD_TRANSPOSE_W = 0x2
 CONVD_MASK_OUTPUT = 0x4
 CONVD_MAX_CHANNELS = 1024               # ch_in, ch_out of the dilated convolution (csrc/dilated_conv.hip)
 CONVD_MAX_TAPS = 16
+CONV2D_RELU_INPUT = 0x1                 # DDSP_CONV2D_* of csrc/conv2d_abi.h
+CONV2D_ADJOINT = 0x2
+CONV2D_MASK_OUTPUT = 0x4
+CONV2D_MAX_CHANNELS = 1024              # ch_in, ch_out of the 2-D convolution (csrc/conv2d.hip)
+CONV2D_MAX_TAPS = 64                    # kh * kw
+CONV2D_MAX_STRIDE = 8
+CONV2D_MAX_SIDE = 2 ** 30               # h, w
 CONV_ADD_DRY = 0x1
 CONV_MASK_TAP0 = 0x2
 CONV_REVERSE_AUDIO = 0x4
@@ -296,6 +310,8 @@ def load():
     norm_entry(lib, name)
   for name in CONV_SIGNATURES:
     conv_entry(lib, name)
+  for name in CONV2D_SIGNATURES:
+    conv2d_entry(lib, name)
   _lib = lib
   return lib
 
@@ -318,6 +334,13 @@ def conv_entry(lib, name):
   """Entry `name` of CONV_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
   fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/dilated_conv.hip
   fn.restype, fn.argtypes = CONV_SIGNATURES[name]
+  return fn
+
+
+def conv2d_entry(lib, name):
+  """Entry `name` of CONV2D_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
+  fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/conv2d.hip
+  fn.restype, fn.argtypes = CONV2D_SIGNATURES[name]
   return fn
 
 

@@ -36,8 +36,14 @@ DILATED CONVOLUTIONS (ddsp/training/nn.py:1153-1323): dilated_conv, Conv2D, Conv
 C ABI csrc/conv_abi.h): matrix cores with fp16 hi / lo operands when ch_out is a multiple of 16, the vector ALU otherwise; no
 padded copy, no atomics, the same bits for a batch row alone and inside a batch.  The weight gradients are K matrix products of
 the framework.  The strided resamplers, FiLM's multiply-add and the residual add are framework ops.
-NOT BUILT (ValueError): spectral_norm=True; and the rest of the reference's nn.py (the ResNet layers, SpectralNormalization,
-SingleGru)."""
+NOT BUILT (ValueError): spectral_norm=True; and the rest of the reference's nn.py (SpectralNormalization, SingleGru).
+
+RESNET (ddsp/training/nn.py:697-839): conv2d, SpatialConv2D, MaxPool2D, NormReluConv, ResidualLayer, ResidualStack, ResNet.
+(ReLU ->) 2-D convolution with 'same' padding and strides on both axes (+ addend), forward and the gradient in x, is ONE kernel
+(csrc/conv2d.hip; C ABI csrc/conv2d_abi.h), the sibling of the dilated one: the product's K axis is the flattened (kh, kw, ch_in),
+no im2col buffer, no padded copy, no atomics.  The normalisations stay on csrc/group_norm.hip; the ReLU behind them rides the
+convolution's load and the residual add its epilogue.  The weight gradients are kh * kw matrix products of the framework; the max
+pool and FiLM's multiply-add are framework ops."""
 import inspect
 import math
 
@@ -1434,3 +1440,328 @@ class OutputSplitsLayer(DictLayer):
   def compute_output(self, *inputs):
     """Takes tensors as input, runs network, and outputs a single tensor (usually [batch, time, channels])."""
     raise NotImplementedError
+
+
+# ------------------ 2-D convolutions and the ResNet ---------------------------
+_conv2d_ws = core.Workspace()
+_DKERNEL_PARTIAL_ELEMENTS = 1 << 24      # 64 MiB of partial kernel gradients per tap, at the most
+
+
+def _conv2d_entry(name):
+  return _lib.conv2d_entry(_lib.load(), name)
+
+
+def same_padding(size, kernel_size, stride):
+  """TF's 'same' rule along one axis (tensorflow/core/framework/kernel_shape_util.cc GetWindowedOutputSizeVerbose):
+  -> (out, before, behind) with out = ceil(size / stride), total = max((out - 1) * stride + kernel_size - size, 0),
+  before = total // 2 and the odd cell behind."""
+  size, kernel_size, stride = int(size), int(kernel_size), int(stride)
+  out = -(-size // stride)
+  total = max((out - 1) * stride + kernel_size - size, 0)
+  return out, total // 2, total - total // 2
+
+
+def _run_conv2d(x, kernel, bias, strides, flags, image=None, mask_src=None, addend=None):
+  """One ddsp_conv2d_f32 call on contiguous fp32 tensors; kernel [kh, kw, ch_in, ch_out].  Forward: x [b, h, w, ch_in] ->
+  [b, out_h, out_w, ch_out].  With CONV2D_ADJOINT x is the gradient [b, out_h, out_w, ch_out], `image` the forward input's (h, w),
+  -> [b, h, w, ch_in]."""
+  kh, kw, ch_in, ch_out = kernel.shape
+  b = x.shape[0]
+  if flags & _lib.CONV2D_ADJOINT:
+    h, w = image
+    y = torch.empty((b, h, w, ch_in), dtype=torch.float32, device=x.device)
+  else:
+    h, w = x.shape[1], x.shape[2]
+    y = torch.empty((b, same_padding(h, kh, strides[0])[0], same_padding(w, kw, strides[1])[0], ch_out), dtype=torch.float32,
+                    device=x.device)
+  if b:
+    ptr = lambda v: None if v is None else v.data_ptr()
+    shape = (b, h, w, ch_in, ch_out, kh, kw, strides[0], strides[1])
+    ws = _conv2d_ws.get(_conv2d_entry('ddsp_conv2d_workspace_bytes')(*shape, flags), x.device)
+    rc = _conv2d_entry('ddsp_conv2d_f32')(x.data_ptr(), kernel.data_ptr(), ptr(bias), ptr(addend), ptr(mask_src), y.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), *shape, flags, core._stream())
+    _checked(rc, 'ddsp_conv2d_f32')
+  return y
+
+
+class _Conv2dFunction(torch.autograd.Function):
+  """torch.autograd node of the 2-D convolution: (x [b, h, w, ch_in], kernel [kh, kw, ch_in, ch_out], bias [ch_out] or None, addend
+  [b, out_h, out_w, ch_out] or None) -> [b, out_h, out_w, ch_out].  Forward and the gradient in x are C-ABI calls (the same kernel;
+  the adjoint gathers the gradient through the inverse of the position map and multiplies by relu'(x) = (x > 0) in its epilogue).
+  The gradients whose reduction runs over batch * positions are the framework's: kh * kw matrix products over strided views of one
+  padded act(x), and a column sum.  The addend's gradient is grad_y.  Kept for the backward: x and the kernel."""
+
+  @staticmethod
+  def forward(ctx, x, kernel, bias, addend, strides, relu_input):
+    y = _run_conv2d(x, kernel, bias, strides, _lib.CONV2D_RELU_INPUT if relu_input else 0, addend=addend)
+    ctx.save_for_backward(x, kernel)
+    ctx.strides, ctx.relu_input, ctx.has_bias, ctx.has_addend = strides, relu_input, bias is not None, addend is not None
+    return y
+
+  @staticmethod
+  def backward(ctx, grad_y):
+    x, kernel = ctx.saved_tensors
+    kh, kw, ch_in, ch_out = kernel.shape
+    (sh, sw), (h, w) = ctx.strides, x.shape[1:3]
+    grad_y = core.tf_float32(grad_y)
+    dx = dk = db = None
+    if ctx.needs_input_grad[0]:
+      flags = _lib.CONV2D_ADJOINT | (_lib.CONV2D_MASK_OUTPUT if ctx.relu_input else 0)
+      dx = _run_conv2d(grad_y, kernel, None, ctx.strides, flags, image=(h, w), mask_src=x if ctx.relu_input else None)
+    if ctx.needs_input_grad[1]:
+      (out_h, top, bottom), (out_w, left, right) = same_padding(h, kh, sh), same_padding(w, kw, sw)
+      a = torch.nn.functional.pad(torch.relu(x) if ctx.relu_input else x, (0, 0, left, right, top, bottom))   # the one copy
+      # One long reduction over batch * positions would run on a handful of workgroups: it is cut into groups - image rows while
+      # their [groups, ch_in, ch_out] partial products stay small, batch rows otherwise - one batched product each, summed after.
+      groups = x.shape[0] * out_h if x.shape[0] * out_h * ch_in * ch_out <= _DKERNEL_PARTIAL_ELEMENTS else x.shape[0]
+      g = grad_y.reshape(groups, -1, ch_out)
+      dk = torch.empty_like(kernel)
+      for i in range(kh):
+        for j in range(kw):                             # y[oh, ow] takes a[oh sh + i, ow sw + j]: a strided view
+          view = a[:, i:i + (out_h - 1) * sh + 1:sh, j:j + (out_w - 1) * sw + 1:sw, :]
+          dk[i, j] = torch.matmul(view.reshape(groups, -1, ch_in).transpose(1, 2), g).sum(0)
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+      db = grad_y.reshape(-1, ch_out).sum(0)
+    return dx, dk, db, (grad_y if ctx.has_addend and ctx.needs_input_grad[3] else None), None, None
+
+
+def _pair(value, what):
+  """(a, b) of an int or a pair, each at least 1."""
+  pair = tuple(value) if isinstance(value, (tuple, list)) else (value, value)
+  if len(pair) != 2 or min(int(v) for v in pair) < 1:
+    raise ValueError('{} must be an int or a pair of ints, each at least 1, got {!r}'.format(what, value))
+  return int(pair[0]), int(pair[1])
+
+
+def conv2d(x, kernel, bias=None, strides=(1, 1), relu_input=False, addend=None):
+  """A 2-D convolution of a channel-last tensor with TF 'same' padding and strides on both axes - tf.keras.layers.Conv2D(ch_out,
+  (kh, kw), strides, padding='same') on [batch, h, w, ch_in] - with an optional ReLU on its input and an optional addend on its
+  output, in one kernel each way (csrc/conv2d.hip; C ABI csrc/conv2d_abi.h):
+
+    y[b, oh, ow, co] = addend + bias[co] + sum_{i, j, ci} act(x[b, oh * sh + i - top, ow * sw + j - left, ci]) * kernel[i, j, ci, co]
+
+  positions outside the image contributing 0; out, top and left per axis are same_padding's.  ReLU is applied as x is loaded, bias
+  and addend as y is written; there is no padded copy and nothing of size [batch, positions, kh * kw * ch_in].  ch_out in multiples
+  of 16 runs on the matrix cores (fp16 hi / lo operands behind a power-of-two scale per batch row of x; the K axis is the flattened
+  (i, j, ci)), every other width on the vector ALU.  The same bits on every run, for a row alone and for any sub-batch.
+
+  Args:
+    x: [batch, h, w, ch_in], of any layout or dtype.
+    kernel: [kh, kw, ch_in, ch_out], the Keras layout.
+    bias: [ch_out] or None.
+    strides: (sh, sw) or one int for both.
+    relu_input: Apply ReLU to x first (its gradient at 0 is 0, as tf.nn.relu's).
+    addend: [batch, out_h, out_w, ch_out] or None: added to the result in the kernel's epilogue (a residual connection).
+
+  Returns:
+    [batch, out_h, out_w, ch_out].  Differentiable in x, kernel, bias and addend.
+
+  Raises:
+    ValueError: shapes that do not fit, or beyond the limits of the MI355X path - ch_in, ch_out <= 1024, kh * kw <= 64,
+      strides <= 8, h, w <= 2 ** 30 and every element count < 2 ** 31.  Checked before anything touches the device.
+  """
+  x_shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(torch.as_tensor(x).shape)
+  k_shape = tuple(kernel.shape) if hasattr(kernel, 'shape') else tuple(torch.as_tensor(kernel).shape)
+  if len(x_shape) != 4:
+    raise ValueError('conv2d: x must be [batch, h, w, ch_in], got {}'.format(x_shape))
+  if len(k_shape) != 4:
+    raise ValueError('conv2d: kernel must be [kh, kw, ch_in, ch_out], got {}'.format(k_shape))
+  sh, sw = _pair(strides, 'conv2d: strides')
+  batch, h, w, ch_in = x_shape
+  kh, kw, _, ch_out = k_shape
+  if k_shape[2] != ch_in or min(h, w, ch_in, ch_out, kh, kw) < 1:
+    raise ValueError('conv2d: x {} and kernel {} must agree in ch_in, and h, w, kh, kw and the channels be at least 1'.format(
+        x_shape, k_shape))
+  if bias is not None and tuple(bias.shape) != (ch_out,):
+    raise ValueError('conv2d: bias must be [ch_out] = {}, got {}'.format((ch_out,), tuple(bias.shape)))
+  if max(ch_in, ch_out) > _lib.CONV2D_MAX_CHANNELS or kh * kw > _lib.CONV2D_MAX_TAPS or max(sh, sw) > _lib.CONV2D_MAX_STRIDE:
+    raise ValueError('conv2d: at most {} channels, {} taps and stride {} on the MI355X path, got ch_in = {}, ch_out = {}, kernel {} x {}, '
+                     'strides {}'.format(_lib.CONV2D_MAX_CHANNELS, _lib.CONV2D_MAX_TAPS, _lib.CONV2D_MAX_STRIDE, ch_in, ch_out, kh, kw,
+                                         (sh, sw)))
+  out_h, out_w = same_padding(h, kh, sh)[0], same_padding(w, kw, sw)[0]
+  if max(h, w) > _lib.CONV2D_MAX_SIDE or max(batch * h * w * ch_in, batch * out_h * out_w * ch_out, kh * kw * ch_in * ch_out) >= 2 ** 31:
+    raise ValueError('conv2d: h and w must stay at or below 2 ** 30 and batch * h * w * ch_in, batch * out_h * out_w * ch_out and the '
+                     'kernel below 2 ** 31 elements, got x {}, kernel {}, strides {}'.format(x_shape, k_shape, (sh, sw)))
+  if addend is not None and tuple(addend.shape) != (batch, out_h, out_w, ch_out):
+    raise ValueError('conv2d: addend must be [batch, out_h, out_w, ch_out] = {}, got {}'.format((batch, out_h, out_w, ch_out),
+                                                                                            tuple(addend.shape)))
+  x, kernel = core.tf_float32(x), core.tf_float32(kernel)
+  bias = None if bias is None else core.tf_float32(bias)
+  addend = None if addend is None else core.tf_float32(addend)
+  if core._needs_grad(x, kernel, bias, addend):
+    return _Conv2dFunction.apply(x, kernel, bias, addend, (sh, sw), bool(relu_input))
+  return _Conv2dFunction.forward(core._NoCtx(), x, kernel, bias, addend, (sh, sw), bool(relu_input))
+
+
+class SpatialConv2D(_Lazy):
+  """tf.keras.layers.Conv2D(filters, (kh, kw), (sh, sw), padding='same') on [batch, h, w, ch]: conv2d, one kernel each way, the 1 x 1
+  projections included.  Weights under the Keras names and layouts: kernel [kh, kw, in, out] ('glorot_uniform' with fans
+  kh * kw * in and kh * kw * out), bias [out] zeros.  (Conv2D is the (k, 1) layer over time of the dilated stack.)"""
+
+  def __init__(self, filters, kernel_size, strides=(1, 1), kernel_initializer='glorot_uniform'):
+    super().__init__()
+    self.filters = int(filters)
+    if self.filters < 1:
+      raise ValueError('SpatialConv2D: filters must be at least 1, got {!r}'.format(filters))
+    self.kernel_size = _pair(kernel_size, 'SpatialConv2D: kernel_size')
+    self.strides = _pair(strides, 'SpatialConv2D: strides')
+    if kernel_initializer != 'glorot_uniform':
+      raise ValueError("SpatialConv2D: kernel_initializer must be 'glorot_uniform', got {!r}".format(kernel_initializer))
+    self.kernel_initializer = kernel_initializer
+
+  def build(self, in_ch):
+    kh, kw = self.kernel_size
+    limit = math.sqrt(6.0 / (kh * kw * in_ch + kh * kw * self.filters))
+    self.kernel = self._param(torch.empty((kh, kw, in_ch, self.filters), dtype=torch.float32).uniform_(-limit, limit))
+    self.bias = self._param(torch.zeros(self.filters))
+    self.built = True
+
+  def forward(self, x, relu_input=False, addend=None):
+    self._ensure_built(x.shape[-1])
+    return conv2d(x, self.kernel, self.bias, self.strides, relu_input, addend)
+
+
+class MaxPool2D(torch.nn.Module):
+  """tf.keras.layers.MaxPool2D(pool_size, strides, padding) on [batch, h, w, ch] (framework ops).  padding='same' is TF's rule
+  (same_padding: the odd cell behind, which F.max_pool2d's own symmetric padding is not); the padded cells are -inf and never win."""
+
+  def __init__(self, pool_size=(2, 2), strides=None, padding='same'):
+    super().__init__()
+    self.pool_size = _pair(pool_size, 'MaxPool2D: pool_size')
+    self.strides = self.pool_size if strides is None else _pair(strides, 'MaxPool2D: strides')
+    if padding not in ('same', 'valid'):
+      raise ValueError("MaxPool2D: padding must be 'same' or 'valid', got {!r}".format(padding))
+    self.padding = padding
+
+  def forward(self, x):
+    if len(x.shape) != 4:
+      raise ValueError('MaxPool2D: x must be [batch, h, w, ch], got {}'.format(tuple(x.shape)))
+    x = core.tf_float32(x).permute(0, 3, 1, 2)
+    if self.padding == 'same':
+      (_, top, bottom), (_, left, right) = (same_padding(n, k, s) for n, k, s in zip(x.shape[2:], self.pool_size, self.strides))
+      x = torch.nn.functional.pad(x, (left, right, top, bottom), value=float('-inf'))
+    return torch.nn.functional.max_pool2d(x, self.pool_size, self.strides).permute(0, 2, 3, 1)
+
+
+class NormReluConv(torch.nn.Module):
+  """Norm -> ReLU -> Conv layer (ddsp/training/nn.py:698-709): Normalize (csrc/group_norm.hip), then conv2d with the ReLU on its
+  load; `addend` rides the convolution's epilogue.  Weights: norm.scale, norm.shift, conv.kernel, conv.bias."""
+
+  def __init__(self, ch, k, s, norm_type):
+    """Downsample frequency by stride."""
+    super().__init__()
+    self.norm = Normalize(norm_type)
+    self.conv = SpatialConv2D(ch, (k, k), (1, s))
+
+  def forward(self, x, addend=None):
+    return self.conv(self.norm(x), relu_input=True, addend=addend)
+
+
+class ResidualLayer(torch.nn.Module):
+  """A single layer for ResNet, with a bottleneck (ddsp/training/nn.py:712-756).  The ReLU behind norm_input is applied by the two
+  convolutions that read it, on their loads, and x + r by the last convolution's epilogue."""
+
+  def __init__(self, ch, stride, shortcut, norm_type, conditional, shift_only):
+    """Downsample frequency by stride, upsample channels by 4."""
+    super().__init__()
+    ch_out = 4 * ch
+    self.shortcut = shortcut
+    self.conditional = conditional
+
+    # Layers.
+    self.norm_input = get_norm(norm_type, conditional, shift_only)
+
+    if self.shortcut:
+      self.conv_proj = SpatialConv2D(ch_out, (1, 1), (1, stride))
+    self.bottleneck = torch.nn.ModuleList([
+        SpatialConv2D(ch, (1, 1), (1, 1)),
+        NormReluConv(ch, 3, stride, norm_type),
+        NormReluConv(ch_out, 1, 1, norm_type),
+    ])
+
+  def forward(self, inputs):
+    if self.conditional:
+      x, z = inputs
+      r = ensure_4d(core.tf_float32(x))
+      x = self.norm_input((r, ensure_4d(core.tf_float32(z))))
+    else:
+      r = ensure_4d(core.tf_float32(inputs))
+      x = self.norm_input(r)
+
+    # The projection shortcut should come after the first norm and ReLU
+    # since it performs a 1x1 convolution.
+    r = self.conv_proj(x, relu_input=True) if self.shortcut else r
+    x = self.bottleneck[0](x, relu_input=True)
+    x = self.bottleneck[1](x)
+    return self.bottleneck[2](x, addend=r)
+
+
+class ResidualStack(torch.nn.Module):
+  """LayerNorm -> ReLU -> Conv layer (ddsp/training/nn.py:759-802): per (ch, n_layers, stride) one ResidualLayer with the projection
+  shortcut and the stride and n_layers - 1 without, then a Normalize and the nonlinearity.  inputs: x, or [x, z] if conditional."""
+
+  def __init__(self, filters, block_sizes, strides, norm_type, conditional=False, shift_only=False, nonlinearity='relu'):
+    """ResNet layers."""
+    super().__init__()
+    self.conditional = conditional
+    layers = []
+    for (ch, n_layers, stride) in zip(filters, block_sizes, strides):
+
+      # Only the first block per residual_stack uses shortcut and strides.
+      layers.append(ResidualLayer(ch, stride, True, norm_type, conditional, shift_only))
+
+      # Add the additional (n_layers - 1) layers to the stack.
+      for _ in range(1, n_layers):
+        layers.append(ResidualLayer(ch, 1, False, norm_type, conditional, shift_only))
+
+    layers.append(Normalize(norm_type))
+    self.layers = torch.nn.ModuleList(layers)
+    self.activation = get_nonlinearity(nonlinearity)
+
+  def forward(self, inputs):
+    if self.conditional:
+      x, z = inputs
+      z = core.tf_float32(z)                            # once: every layer reads the same fp32 tensor, and its gradient is one fp32 sum
+    else:
+      x = inputs
+
+    for layer in self.layers:
+      is_cond = self.conditional and isinstance(layer, ResidualLayer)
+      l_in = [x, z] if is_cond else x
+      x = layer(l_in)
+    return self.activation(x)
+
+
+class ResNet(torch.nn.Module):
+  """Residual network (ddsp/training/nn.py:805-839): a 7 x 7 stem striding the second axis by 2, a (1, 3) max pool striding it by 2,
+  and two ResidualStacks; [batch, frames, bins, 1] -> [batch, frames, ceil(bins / 32), 32 ch].  An unknown size raises the
+  reference's KeyError.  inputs: x, or [x, z] if conditional."""
+
+  def __init__(self, size='large', norm_type='layer', conditional=False, shift_only=False):
+    super().__init__()
+    self.conditional = conditional
+    size_dict = {
+        'small': (32, [2, 3, 4]),
+        'medium': (32, [3, 4, 6]),
+        'large': (64, [3, 4, 6]),
+    }
+    ch, blocks = size_dict[size]
+    self.layers = torch.nn.ModuleList([
+        SpatialConv2D(64, (7, 7), (1, 2)),
+        MaxPool2D(pool_size=(1, 3), strides=(1, 2), padding='same'),
+        ResidualStack([ch, 2 * ch, 4 * ch], blocks, [1, 2, 2], norm_type, conditional, shift_only),
+        ResidualStack([8 * ch], [3], [2], norm_type, conditional, shift_only)
+    ])
+
+  def forward(self, inputs):
+    if self.conditional:
+      x, z = inputs
+      z = core.tf_float32(z)
+    else:
+      x = inputs
+
+    for layer in self.layers:
+      is_cond = self.conditional and isinstance(layer, ResidualStack)
+      l_in = [x, z] if is_cond else x
+      x = layer(l_in)
+    return x
