@@ -8,18 +8,12 @@
 // Forward and adjoint are ONE kernel: they differ in source_position() (output position, tap -> source position or none: the
 // adjoint gathers the gradient at (r + top - i) / sh where the division is exact) and in how conv2d_pack_kernel reads W.
 //
-//   conv2d_mfma_kernel    produced width a multiple of 16.  A block owns a run of 64 output positions of one batch row (16 per
-//                         wavefront; the run is over the flattened (oh, ow), so it crosses image rows where out_w is small and each
-//                         lane resolves its own position) and up to 128 produced channels (8 column tiles, 64 accumulator
-//                         registers per lane).  Per 32-deep step of K the block stages the step's weight fragments in LDS once for
-//                         its four wavefronts; each lane loads its 8 K values of its position - with the source width a multiple
-//                         of 8 they are 32 contiguous bytes of one tap, otherwise (the stem: one channel, 49 taps in two steps)
-//                         eight positions - applies ReLU and the row's power-of-two scale, splits into fp16 hi / lo ONCE and
-//                         multiplies by the staged fragments: hi hi + hi lo + lo hi as in split_f16.h.  Both loads run one step
-//                         ahead, into registers; two stages in LDS, one barrier per step.  The epilogue rescales, adds the bias,
-//                         multiplies by relu'(mask_src) and adds the addend.
-//   conv2d_absmax_kernel  the largest magnitude of W (up to 64 partials) and of act(x) per BATCH ROW (up to 16 each): what the
-//                         power-of-two scales come from.  Never per call for x: a row alone gives the bits it gives inside a batch.
+//   conv2d_mfma_kernel    produced width a multiple of 16: the matrix-core product conv_mfma.h describes (its power-of-two
+//                         scales, its workspace) over a run of 64 output positions of one batch row; the run is over the flattened
+//                         (oh, ow), so it crosses image rows where out_w is small and each lane resolves its own position.  A step
+//                         is 32 K rows: each lane loads its 8 K values of its position - with the source width a multiple of 8
+//                         they are 32 contiguous bytes of one tap, otherwise (the stem: one channel, 49 taps in two steps) eight
+//                         positions.
 //   conv2d_pack_kernel    W as MFMA B fragments over the flattened K axis, fp16 hi / lo behind 2^-e, once per call; the K tail is 0.
 //   conv2d_plain_kernel   the vector-ALU form for every other width: a thread per output element, taps and channels in order.
 //
@@ -31,21 +25,12 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "conv2d_abi.h"
-#include "common.h"
-#include "launch.h"
-#include "split_f16.h"
+#include "conv_mfma.h"
 
 namespace ddsp {
 namespace conv2d {
 
-constexpr int kWeightPartials = 64;        // at most this many blocks in the pass over W
-constexpr int kRowPartials = 16;           // at most this many blocks per batch row in the pass over x
-constexpr size_t kPartialItems = 4096;     // values a block of those passes takes, or more
-constexpr size_t kHeaderBytes = 512;       // workspace: int exponent of W at 0, kWeightPartials floats at 256
-constexpr int kTilePositions = 64;         // output positions of a block: 16 per wavefront
-constexpr int kChunkTiles = 8;             // 16-column tiles of a block
-constexpr int kStageLoads = kChunkTiles * 128 / 256;     // u32x4 a thread moves to stage one step's fragments
-constexpr unsigned kMaxAbsmaxBlocks = 65536;
+using namespace conv_mfma;
 
 // The call as the kernels see it: `src` is what is read (x forward, the gradient in the adjoint), `dst` what is written.
 struct Geometry {
@@ -78,22 +63,6 @@ __device__ __forceinline__ float weight_at(const float* __restrict__ w, const Ge
   return g.adjoint ? w[((size_t)tap * g.dst_ch + col) * g.src_ch + cs] : w[((size_t)tap * g.src_ch + cs) * g.dst_ch + col];
 }
 
-// partials[item] = max of act(v) (ReLU) or |v| over share item % per_row of row item / per_row (n values each); items in turn
-__global__ __launch_bounds__(256) void conv2d_absmax_kernel(const float* __restrict__ v, size_t n, size_t rows, int per_row, int relu,
-                                                            float* __restrict__ partials) {
-  __shared__ float lds[4];
-  for (size_t item = blockIdx.x; item < rows * per_row; item += gridDim.x) {
-    const float* r = v + (item / per_row) * n;
-    float m = 0.0f;
-    for (size_t i = (item % per_row) * 256 + threadIdx.x; i < n; i += (size_t)per_row * 256) m = fmaxf(m, relu ? r[i] : fabsf(r[i]));
-    m = wave_max(m);
-    __syncthreads();                                     // the previous item's reader is done
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[item] = fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-  }
-}
-
 // MFMA B fragments, scaled by 2^-e, as fp16 hi / lo: fragment (ks, ct), part p at u32x4 index ((ks CT + ct) 2 + p) 64 + lane; lane l,
 // element q holds B[kk][col], kk = 32 ks + 8 (l / 16) + q, col = 16 ct + l % 16, and 0 where kk >= kh kw src_ch.  The column tiles
 // of one step lie side by side: a block stages a run of them.
@@ -117,22 +86,7 @@ __global__ __launch_bounds__(256) void conv2d_pack_kernel(const float* __restric
     const int kk = k0 + q;
     v[q] = kk < KT ? ldexpf(weight_at(w, g, kk / g.src_ch, kk % g.src_ch, col), -e) : 0.0f;
   }
-  f16x8 hi, lo;
-  split8(v, hi, lo);
-  packed[frag_id * 128 + lane] = __builtin_bit_cast(u32x4, hi);
-  packed[frag_id * 128 + 64 + lane] = __builtin_bit_cast(u32x4, lo);
-}
-
-// what every output element goes through after its sum
-__device__ __forceinline__ float epilogue(float sum, size_t at, int col, const float* __restrict__ bias, const float* __restrict__ addend,
-                                          const float* __restrict__ mask_src) {
-  if (bias) sum += bias[col];
-  if (mask_src) {                                        // relu'(x): 1 above 0, 0 at and below; where x is a NaN the gradient is one too
-    const float m = mask_src[at];
-    sum = m > 0.0f ? sum : (m != m ? m : 0.0f);
-  }
-  if (addend) sum += addend[at];
-  return sum;
+  store_fragment(packed, frag_id, lane, v);
 }
 
 // grid (batch * tiles, column chunks)
@@ -268,13 +222,6 @@ __global__ __launch_bounds__(256) void conv2d_plain_kernel(const float* __restri
   y[at] = epilogue(sum, at, col, bias, addend, mask_src);
 }
 
-static inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-// blocks a pass over n values is split into: one per kPartialItems, between 1 and `most`
-static inline int partials_for(size_t n, int most) {
-  const size_t p = n / kPartialItems;
-  return (int)(p < 1 ? 1 : (p > (size_t)most ? (size_t)most : p));
-}
-static inline size_t row_partial_bytes(int batch) { return align256((size_t)batch * kRowPartials * sizeof(float)); }
 static inline size_t packed_bytes(int src_ch, int dst_ch, int taps) {
   return (((size_t)taps * src_ch + 31) / 32) * (dst_ch / 16) * 128 * sizeof(u32x4);
 }
@@ -316,7 +263,7 @@ extern "C" size_t ddsp_conv2d_workspace_bytes(int batch, int h, int w, int ch_in
   const int adjoint = (flags & DDSP_CONV2D_ADJOINT) ? 1 : 0;
   const int src_ch = adjoint ? ch_out : ch_in, dst_ch = adjoint ? ch_in : ch_out;
   if (dst_ch % 16 != 0) return 0;
-  return kHeaderBytes + row_partial_bytes(batch) + packed_bytes(src_ch, dst_ch, kh * kw);
+  return fragments_offset(batch) + packed_bytes(src_ch, dst_ch, kh * kw);
 }
 
 extern "C" int ddsp_conv2d_f32(const float* x, const float* W, const float* bias, const float* addend, const float* mask_src, float* y,
@@ -339,21 +286,14 @@ extern "C" int ddsp_conv2d_f32(const float* x, const float* W, const float* bias
   }
   if (!workspace) return DDSP_ERR_NULL_POINTER;
   if (workspace_bytes < ddsp_conv2d_workspace_bytes(batch, h, w, ch_in, ch_out, kh, kw, sh, sw, flags)) return DDSP_ERR_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  int* exponent = reinterpret_cast<int*>(ws);
-  float* w_partials = reinterpret_cast<float*>(ws + 256);
-  float* row_partials = reinterpret_cast<float*>(ws + kHeaderBytes);
-  u32x4* packed = reinterpret_cast<u32x4*>(ws + kHeaderBytes + row_partial_bytes(batch));
-  const size_t n_w = (size_t)kh * kw * ch_in * ch_out, n_row = (size_t)g.src_h * g.src_w * g.src_ch;
-  const int w_blocks = partials_for(n_w, kWeightPartials), per_row = partials_for(n_row, kRowPartials);
-  hipLaunchKernelGGL(conv2d_absmax_kernel, dim3(w_blocks), dim3(256), 0, s, W, n_w, (size_t)1, w_blocks, 0, w_partials);
-  const size_t items = (size_t)batch * per_row;
-  hipLaunchKernelGGL(conv2d_absmax_kernel, dim3((unsigned)(items < kMaxAbsmaxBlocks ? items : kMaxAbsmaxBlocks)), dim3(256), 0, s, x,
-                     n_row, (size_t)batch, per_row, relu, row_partials);
+  const Workspace ws = carve(workspace, batch);
+  const Partials p = launch_absmax(ws, W, (size_t)kh * kw * ch_in * ch_out, x, (size_t)g.src_h * g.src_w * g.src_ch, batch, relu, s);
   const size_t pack_threads = (((size_t)kh * kw * g.src_ch + 31) / 32) * (g.dst_ch / 16) * 64;
-  hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)((pack_threads + 255) / 256)), dim3(256), 0, s, W, w_partials, exponent, packed, g, w_blocks);
+  hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)((pack_threads + 255) / 256)), dim3(256), 0, s, W, ws.w_partials, ws.exponent, ws.packed, g,
+                     p.w_blocks);
   const int tiles = (int)((positions + kTilePositions - 1) / kTilePositions);
   const dim3 grid((unsigned)((size_t)batch * tiles), (unsigned)((g.dst_ch / 16 + kChunkTiles - 1) / kChunkTiles));
-  hipLaunchKernelGGL(conv2d_mfma_kernel, grid, dim3(256), 0, s, x, packed, exponent, row_partials, bias, addend, mask, y, g, relu, tiles, per_row);
+  hipLaunchKernelGGL(conv2d_mfma_kernel, grid, dim3(256), 0, s, x, ws.packed, ws.exponent, ws.row_partials, bias, addend, mask, y, g, relu, tiles,
+                     p.per_row);
   return check_launch();
 }

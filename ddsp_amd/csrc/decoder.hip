@@ -266,10 +266,7 @@ __global__ __launch_bounds__(256) void gru_pack_kernel(const float* __restrict__
     if (k < H) a = transposed ? r[(size_t)(jt * 16 + j) * 3 * H + (size_t)g * H + k] : r[(size_t)k * 3 * H + (size_t)g * H + jt * 16 + j];
     v[q] = ldexpf(a, -e);
   }
-  f16x8 hi, lo;
-  split8(v, hi, lo);
-  packed[frag_id * 128 + lane] = __builtin_bit_cast(u32x4, hi);
-  packed[frag_id * 128 + 64 + lane] = __builtin_bit_cast(u32x4, lo);
+  store_fragment(packed, frag_id, lane, v);
 }
 
 // the gate arithmetic of one (row, unit) at step t, and everything that is written for it

@@ -5,18 +5,11 @@
 //
 // No padded copy, no im2col: a tap is a row offset, rows outside [0, time) are zeros in the fragment.
 //
-//   conv_mfma_kernel    ch_out a multiple of 16.  A block owns 64 time rows of one batch row (a 16-row tile per wavefront) and up
-//                       to 128 output channels (8 column tiles, 64 accumulator registers per lane).  Per (tap, 32-deep step of
-//                       ch_in) the block stages the step's weight fragments in LDS once for its four wavefronts; each wavefront
-//                       loads its 16 rows of x for the tap (32 bytes per lane, ReLU and the row's power-of-two scale applied on
-//                       the way), splits them into fp16 hi / lo ONCE and multiplies by the staged fragments: hi hi + hi lo + lo hi
-//                       as in split_f16.h.  Both loads run one step ahead, into registers, behind the matrix products of the
-//                       step before; two stages in LDS, one barrier per step.  The taps' rows overlap between steps and between
+//   conv_mfma_kernel    ch_out a multiple of 16: the matrix-core product conv_mfma.h describes (its power-of-two scales, its
+//                       workspace) over 64 time rows of one batch row.  A step is a (tap, 32-deep slice of ch_in): each wavefront
+//                       loads its 16 rows of x for the tap, 32 bytes per lane.  The taps' rows overlap between steps and between
 //                       neighbouring blocks, so x comes from HBM once and from cache afterwards.  Taps that lie wholly in the
 //                       padding for the block are skipped.
-//                       The epilogue rescales, adds the bias, multiplies by relu'(mask_src) and adds the addend.
-//   conv_absmax_kernel  the largest magnitude of W (up to 64 partials) and of act(x) per BATCH ROW (up to 16 each): what the
-//                       power-of-two scales come from.  Never per call for x: a row alone gives the bits it gives inside a batch.
 //   conv_pack_kernel    W (or the adjoint's taps: reversed and transposed) as MFMA B fragments, fp16 hi / lo behind 2^-e, once per
 //                       call; ch_in tails are zeros.
 //   conv_plain_kernel   the vector-ALU form for every other ch_out: a thread per output element, taps and channels in order.
@@ -29,37 +22,12 @@
 #include <stdint.h>
 #include "../../include/ddsp_amd.h"
 #include "conv_abi.h"
-#include "common.h"
-#include "launch.h"
-#include "split_f16.h"
+#include "conv_mfma.h"
 
 namespace ddsp {
 namespace conv {
 
-constexpr int kWeightPartials = 64;        // at most this many blocks in the pass over W
-constexpr int kRowPartials = 16;           // at most this many blocks per batch row in the pass over x
-constexpr size_t kPartialItems = 4096;     // values a block of those passes takes, or more
-constexpr size_t kHeaderBytes = 512;       // workspace: int exponent of W at 0, kWeightPartials floats at 256
-constexpr int kTileRows = 64;              // time rows of a block: 16 per wavefront
-constexpr int kChunkTiles = 8;             // 16-column tiles of a block
-constexpr int kStageLoads = kChunkTiles * 128 / 256;     // u32x4 a thread moves to stage one step's fragments
-constexpr unsigned kMaxAbsmaxBlocks = 65536;
-
-// partials[item] = max of act(v) (ReLU) or |v| over share item % per_row of row item / per_row (n values each); items in turn
-__global__ __launch_bounds__(256) void conv_absmax_kernel(const float* __restrict__ v, size_t n, size_t rows, int per_row, int relu,
-                                                          float* __restrict__ partials) {
-  __shared__ float lds[4];
-  for (size_t item = blockIdx.x; item < rows * per_row; item += gridDim.x) {
-    const float* r = v + (item / per_row) * n;
-    float m = 0.0f;
-    for (size_t i = (item % per_row) * 256 + threadIdx.x; i < n; i += (size_t)per_row * 256) m = fmaxf(m, relu ? r[i] : fabsf(r[i]));
-    m = wave_max(m);
-    __syncthreads();                                     // the previous item's reader is done
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[item] = fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-  }
-}
+using namespace conv_mfma;
 
 // tap k of the convolution that is computed: [ci][co]
 __device__ __forceinline__ float tap_weight(const float* __restrict__ w, int k, int ci, int co, int Cin, int Cout, int K, int transposed) {
@@ -85,22 +53,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict_
   float v[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) v[q] = c0 + q < Cin ? ldexpf(tap_weight(w, k, c0 + q, co, Cin, Cout, K, transposed), -e) : 0.0f;
-  f16x8 hi, lo;
-  split8(v, hi, lo);
-  packed[frag_id * 128 + lane] = __builtin_bit_cast(u32x4, hi);
-  packed[frag_id * 128 + 64 + lane] = __builtin_bit_cast(u32x4, lo);
-}
-
-// what every output element goes through after its sum
-__device__ __forceinline__ float epilogue(float sum, size_t at, int co, const float* __restrict__ bias, const float* __restrict__ addend,
-                                          const float* __restrict__ mask_src) {
-  if (bias) sum += bias[co];
-  if (mask_src) {                                        // relu'(x): 1 above 0, 0 at and below; where x is a NaN the gradient is one too
-    const float m = mask_src[at];
-    sum = m > 0.0f ? sum : (m != m ? m : 0.0f);
-  }
-  if (addend) sum += addend[at];
-  return sum;
+  store_fragment(packed, frag_id, lane, v);
 }
 
 // grid (batch * tiles, column chunks)
@@ -112,7 +65,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict_
   __shared__ u32x4 stage[2][kChunkTiles * 128];          // the fragments of this block's column tiles for two (tap, step)s: 32 KB
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t b = blockIdx.x / (unsigned)tiles;
-  const long long block_t0 = (long long)(blockIdx.x % (unsigned)tiles) * kTileRows;
+  const long long block_t0 = (long long)(blockIdx.x % (unsigned)tiles) * kTilePositions;
   const int CT = Cout / 16, KS = (Cin + 31) / 32;
   const int ct0 = blockIdx.y * kChunkTiles;
   const int nct = CT - ct0 < kChunkTiles ? CT - ct0 : kChunkTiles;
@@ -126,7 +79,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict_
   int k_lo = K, k_hi = -1;
   for (int k = 0; k < K; ++k) {
     const long long shift = (long long)k * dilation - pad_left;
-    if (block_t0 + shift < T && block_t0 + (kTileRows - 1) + shift >= 0) {
+    if (block_t0 + shift < T && block_t0 + (kTilePositions - 1) + shift >= 0) {
       k_lo = k < k_lo ? k : k_lo;
       k_hi = k;
     }
@@ -229,13 +182,6 @@ __global__ __launch_bounds__(256) void conv_plain_kernel(const float* __restrict
   y[at] = epilogue(sum, at, co, bias, addend, mask_src);
 }
 
-static inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-// blocks a pass over n values is split into: one per kPartialItems, between 1 and `most`
-static inline int partials_for(size_t n, int most) {
-  const size_t p = n / kPartialItems;
-  return (int)(p < 1 ? 1 : (p > (size_t)most ? (size_t)most : p));
-}
-static inline size_t row_partial_bytes(int batch) { return align256((size_t)batch * kRowPartials * sizeof(float)); }
 static inline size_t packed_bytes(int ch_in, int ch_out, int taps) {
   return (size_t)taps * ((ch_in + 31) / 32) * (ch_out / 16) * 128 * sizeof(u32x4);
 }
@@ -255,7 +201,7 @@ using namespace ddsp::conv;
 
 extern "C" size_t ddsp_dilated_conv_workspace_bytes(int batch, int time, int ch_in, int ch_out, int taps) {
   if (!well_formed(batch, time, ch_in, ch_out, taps) || batch == 0 || !supported(batch, time, ch_in, ch_out, taps) || ch_out % 16 != 0) return 0;
-  return kHeaderBytes + row_partial_bytes(batch) + packed_bytes(ch_in, ch_out, taps);
+  return fragments_offset(batch) + packed_bytes(ch_in, ch_out, taps);
 }
 
 extern "C" int ddsp_dilated_conv_f32(const float* x, const float* W, const float* bias, const float* addend, const float* mask_src, float* y,
@@ -278,23 +224,14 @@ extern "C" int ddsp_dilated_conv_f32(const float* x, const float* W, const float
   }
   if (!workspace) return DDSP_ERR_NULL_POINTER;
   if (workspace_bytes < ddsp_dilated_conv_workspace_bytes(batch, time, ch_in, ch_out, taps)) return DDSP_ERR_WORKSPACE;
-  char* ws = static_cast<char*>(workspace);
-  int* exponent = reinterpret_cast<int*>(ws);
-  float* w_partials = reinterpret_cast<float*>(ws + 256);
-  float* row_partials = reinterpret_cast<float*>(ws + kHeaderBytes);
-  u32x4* packed = reinterpret_cast<u32x4*>(ws + kHeaderBytes + row_partial_bytes(batch));
-  const size_t n_w = (size_t)taps * ch_in * ch_out, n_row = (size_t)time * ch_in;
-  const int w_blocks = partials_for(n_w, kWeightPartials), per_row = partials_for(n_row, kRowPartials);
-  hipLaunchKernelGGL(conv_absmax_kernel, dim3(w_blocks), dim3(256), 0, s, W, n_w, (size_t)1, w_blocks, 0, w_partials);
-  const size_t items = (size_t)batch * per_row;
-  hipLaunchKernelGGL(conv_absmax_kernel, dim3((unsigned)(items < kMaxAbsmaxBlocks ? items : kMaxAbsmaxBlocks)), dim3(256), 0, s, x,
-                     n_row, (size_t)batch, per_row, relu, row_partials);
+  const Workspace ws = carve(workspace, batch);
+  const Partials p = launch_absmax(ws, W, (size_t)taps * ch_in * ch_out, x, (size_t)time * ch_in, batch, relu, s);
   const size_t pack_threads = (size_t)taps * ((ch_in + 31) / 32) * (ch_out / 16) * 64;
-  hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((pack_threads + 255) / 256)), dim3(256), 0, s, W, w_partials, exponent, packed, ch_in, ch_out,
-                     taps, transposed, w_blocks);
-  const int tiles = (time + kTileRows - 1) / kTileRows;
+  hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((pack_threads + 255) / 256)), dim3(256), 0, s, W, ws.w_partials, ws.exponent, ws.packed, ch_in,
+                     ch_out, taps, transposed, p.w_blocks);
+  const int tiles = (time + kTilePositions - 1) / kTilePositions;
   const dim3 grid((unsigned)((size_t)batch * tiles), (unsigned)((ch_out / 16 + kChunkTiles - 1) / kChunkTiles));
-  hipLaunchKernelGGL(conv_mfma_kernel, grid, dim3(256), 0, s, x, packed, exponent, row_partials, bias, addend, mask, y, time, ch_in, ch_out, taps,
-                     dilation, pad_left, relu, tiles, per_row);
+  hipLaunchKernelGGL(conv_mfma_kernel, grid, dim3(256), 0, s, x, ws.packed, ws.exponent, ws.row_partials, bias, addend, mask, y, time, ch_in, ch_out,
+                     taps, dilation, pad_left, relu, tiles, p.per_row);
   return check_launch();
 }

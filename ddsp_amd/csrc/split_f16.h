@@ -33,6 +33,14 @@ __device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo
     lo[e] = l;
   }
 }
+// How a pack kernel ends: this lane's 8 values of B fragment `frag_id`, already behind the scale, split and stored where the
+// multiplying kernels read them - part hi at u32x4 index frag_id 128 + lane, part lo 64 further.
+__device__ __forceinline__ void store_fragment(u32x4* packed, size_t frag_id, int lane, const float (&v)[8]) {
+  f16x8 hi, lo;
+  split8(v, hi, lo);
+  packed[frag_id * 128 + lane] = __builtin_bit_cast(u32x4, hi);
+  packed[frag_id * 128 + 64 + lane] = __builtin_bit_cast(u32x4, lo);
+}
 // two fp16 numbers as one dword, `a` in the low half
 __device__ __forceinline__ uint32_t pack(_Float16 a, _Float16 b) {
   return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);

@@ -1,5 +1,7 @@
 """Which kernels' machine code changed?  Compiles every csrc/*.hip to gfx950 assembly (hipcc -S, device only), hashes
-each kernel's instruction stream (symbols, labels and comments normalised away) and compares with a recorded baseline.
+each kernel's instruction stream (symbols, labels and comments normalised away, and without the section directive that
+closes the kernel, so that a kernel may move into a header as a `static __global__`) and compares with a recorded baseline.
+Baselines recorded before that directive was left out do not compare with hashes taken since.
 
     python tools/isa_guard.py --record profiles/r01_isa_hashes.json      # write the baseline
     python tools/isa_guard.py profiles/r01_isa_hashes.json               # list kernels that differ / are new
@@ -24,7 +26,12 @@ def demangled_kernels(asm_path):
   for m in re.finditer(r'^(_Z\w+):\s*; @\1\n(.*?)\n\.Lfunc_end\d+:', txt, re.S | re.M):
     body = re.sub(r'_Z\w+', 'SYM', m.group(2))
     body = re.sub(r'\.L\w+', 'LBL', body)
-    body = '\n'.join(line.split(';')[0].rstrip() for line in body.splitlines())
+    lines = [line.split(';')[0].rstrip() for line in body.splitlines()]
+    # the directive directly before .Lfunc_end says which section the assembler returns to behind the kernel: `.text`, or the
+    # kernel's own section where it has internal linkage (a `static __global__` of a header).  It is no instruction.
+    if lines and lines[-1].split()[:1] in (['.text'], ['.section']):
+      lines.pop()
+    body = '\n'.join(lines)
     out[m.group(1)] = hashlib.sha1(body.encode()).hexdigest()[:16]
   if not out:
     return out
