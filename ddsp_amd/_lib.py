@@ -216,6 +216,14 @@ CONV2D_SIGNATURES = {
     'ddsp_conv2d_f32': (c_int, [c_f32p] * 6 + [c_voidp, c_size_t] + [c_int] * 9 + [c_uint, c_voidp]),
 }
 
+# name -> (restype, argtypes) of the entries of csrc/vq_abi.h (training.nn's vq_assign / vq_statistics / VectorQuantization), typed
+# by vq_entry(): a table of its own for the same reason.
+VQ_SIGNATURES = {
+    'ddsp_vq_workspace_bytes': (c_size_t, [c_int] * 2),
+    'ddsp_vq_assign_f32': (c_int, [c_f32p] * 4 + [c_voidp, c_size_t] + [c_int] * 4 + [c_voidp]),
+    'ddsp_vq_statistics_f32': (c_int, [c_f32p] * 4 + [c_int] * 4 + [c_voidp]),
+}
+
 # flags (mirror include/ddsp_amd.h)
 HARM_SCALE_EXP_SIGMOID = 0x1
 HARM_NORMALIZE_NYQUIST = 0x2
@@ -269,6 +277,8 @@ CONV2D_MAX_CHANNELS = 1024              # ch_in, ch_out of the 2-D convolution (
 CONV2D_MAX_TAPS = 64                    # kh * kw
 CONV2D_MAX_STRIDE = 8
 CONV2D_MAX_SIDE = 2 ** 30               # h, w
+VQ_MAX_CENTROIDS = 4096                 # DDSP_VQ_* of csrc/vq_abi.h: k and the width of a head of the vector quantizer (csrc/vq.hip)
+VQ_MAX_DIMS = 512
 CONV_ADD_DRY = 0x1
 CONV_MASK_TAP0 = 0x2
 CONV_REVERSE_AUDIO = 0x4
@@ -312,6 +322,8 @@ def load():
     conv_entry(lib, name)
   for name in CONV2D_SIGNATURES:
     conv2d_entry(lib, name)
+  for name in VQ_SIGNATURES:
+    vq_entry(lib, name)
   _lib = lib
   return lib
 
@@ -341,6 +353,13 @@ def conv2d_entry(lib, name):
   """Entry `name` of CONV2D_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
   fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/conv2d.hip
   fn.restype, fn.argtypes = CONV2D_SIGNATURES[name]
+  return fn
+
+
+def vq_entry(lib, name):
+  """Entry `name` of VQ_SIGNATURES on `lib` (whatever load() returned), typed; typing twice changes nothing."""
+  fn = getattr(lib, name)         # AttributeError here == the library was built without csrc/vq.hip
+  fn.restype, fn.argtypes = VQ_SIGNATURES[name]
   return fn
 
 

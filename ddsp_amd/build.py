@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ['harmonic.hip', 'harmonic_table.hip', 'harmonic_bwd_table.hip', 'filtered_noise.hip', 'filtered_noise_mfma.hip', 'filtered_noise_general.hip', 'reverb.hip', 'spectral_loss.hip', 'spectral_loss_det.hip', 'spectral_terms.hip', 'general.hip', 'wavetable.hip', 'sinusoidal.hip', 'consistency.hip', 'wasserstein.hip', 'hmm.hip', 'notes.hip', 'features.hip', 'fir_grad.hip', 'profile.hip', 'scale_fns.hip', 'critical_bands.hip', 'harmonic_wavetable.hip', 'decoder.hip', 'group_norm.hip', 'dilated_conv.hip', 'conv2d.hip']
+SOURCES = ['harmonic.hip', 'harmonic_table.hip', 'harmonic_bwd_table.hip', 'filtered_noise.hip', 'filtered_noise_mfma.hip', 'filtered_noise_general.hip', 'reverb.hip', 'spectral_loss.hip', 'spectral_loss_det.hip', 'spectral_terms.hip', 'general.hip', 'wavetable.hip', 'sinusoidal.hip', 'consistency.hip', 'wasserstein.hip', 'hmm.hip', 'notes.hip', 'features.hip', 'fir_grad.hip', 'profile.hip', 'scale_fns.hip', 'critical_bands.hip', 'harmonic_wavetable.hip', 'decoder.hip', 'group_norm.hip', 'dilated_conv.hip', 'conv2d.hip', 'vq.hip']
 OUT = os.path.join(HERE, 'lib', 'libddsp_amd.so')
 
 

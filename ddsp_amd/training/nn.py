@@ -36,14 +36,24 @@ DILATED CONVOLUTIONS (ddsp/training/nn.py:1153-1323): dilated_conv, Conv2D, Conv
 C ABI csrc/conv_abi.h): matrix cores with fp16 hi / lo operands when ch_out is a multiple of 16, the vector ALU otherwise; no
 padded copy, no atomics, the same bits for a batch row alone and inside a batch.  The weight gradients are K matrix products of
 the framework.  The strided resamplers, FiLM's multiply-add and the residual add are framework ops.
-NOT BUILT (ValueError): spectral_norm=True; and the rest of the reference's nn.py (SpectralNormalization, SingleGru).
+NOT BUILT (ValueError): spectral_norm=True; and SpectralNormalization itself.
 
 RESNET (ddsp/training/nn.py:697-839): conv2d, SpatialConv2D, MaxPool2D, NormReluConv, ResidualLayer, ResidualStack, ResNet.
 (ReLU ->) 2-D convolution with 'same' padding and strides on both axes (+ addend), forward and the gradient in x, is ONE kernel
 (csrc/conv2d.hip; C ABI csrc/conv2d_abi.h), the sibling of the dilated one: the product's K axis is the flattened (kh, kw, ch_in),
 no im2col buffer, no padded copy, no atomics.  The normalisations stay on csrc/group_norm.hip; the ReLU behind them rides the
 convolution's load and the residual add its epilogue.  The weight gradients are kh * kw matrix products of the framework; the max
-pool and FiLM's multiply-add are framework ops."""
+pool and FiLM's multiply-add are framework ops.
+
+VECTOR QUANTIZATION (ddsp/training/nn.py:1342-1461): vq_assign, vq_statistics, VectorQuantization.  The nearest centroid of every
+vector and the per-centroid counts and sums of a batch are fused kernels (csrc/vq.hip; C ABI csrc/vq_abi.h): the reference's
+[n, k] distance and one-hot matrices are never built, the heads are read in place.  Matrix cores with fp16 hi / lo operands when k
+is a multiple of 16, the vector ALU otherwise; ties go to the lowest index; fp64 sums in a fixed order, no atomics.  The centroids,
+the restarts and the moving averages are framework ops on [k, D].
+Limits (NotImplementedError): k <= 4096, depth / num_heads <= 512, rows * num_heads below 2 ** 31.
+
+THE REST (ddsp/training/nn.py:343-356, 615-694, 1141-1149): straight_through_softmax, straight_through_choice, polyphase_resample,
+PolyphaseResample (framework ops, on host tensors too) and SingleGru (the GRU and LayerNormalization above)."""
 import inspect
 import math
 
@@ -61,6 +71,28 @@ def straight_through_int_quantization(x):
   gradients as if no quantization happened.  Framework ops."""
   x = core.tf_float32(x)
   return x + (torch.round(x) - x).detach()
+
+
+def straight_through_softmax(logits):
+  """Straight-through estimator of a one-hot categorical distribution (ddsp/training/nn.py:343-350).
+
+  Returns (sample, probs): probs = softmax(logits) over the last axis; sample is one draw per distribution from torch's generator,
+  one-hot in value - stop_gradient(sample - probs * sample) + probs * sample - with the gradient of probs * sample.  Framework ops,
+  on the tensor's own device (host tensors too)."""
+  logits = torch.as_tensor(logits)
+  logits = logits if logits.is_floating_point() else logits.to(torch.float32)
+  probs = torch.softmax(logits, dim=-1)
+  flat = probs.detach().reshape(-1, probs.shape[-1])
+  drawn = torch.multinomial(flat, 1) if flat.numel() else torch.zeros((flat.shape[0], 1), dtype=torch.int64, device=flat.device)
+  sample = torch.zeros_like(flat).scatter_(1, drawn, 1.0).reshape(probs.shape)
+  p_sample = probs * sample
+  return (sample - p_sample).detach() + p_sample, probs
+
+
+def straight_through_choice(logits, values):
+  """Straight-through estimator of choosing a value using a boolean mask (ddsp/training/nn.py:353-356): [..., n] -> [..., 1]."""
+  choice, _ = straight_through_softmax(logits)
+  return torch.sum(choice * torch.as_tensor(values, device=choice.device), dim=-1, keepdim=True)
 
 
 # ------------------ plumbing ---------------------------------------------------
@@ -995,6 +1027,74 @@ class RnnSandwich(_Sequential):
     super().__init__([FcStack(fc_stack_ch, fc_stack_layers), Rnn(rnn_ch, rnn_type), FcStack(fc_stack_ch, fc_stack_layers)])
 
 
+class SingleGru(_Sequential):
+  """GRU(gru_dim, return_sequences=True) -> LayerNormalization (ddsp/training/nn.py:1141-1149)."""
+
+  def __init__(self, gru_dim=128):
+    super().__init__([GRU(gru_dim, return_sequences=True), LayerNormalization()])
+
+
+# ------------------ Resampling ------------------------------------------------
+def polyphase_resample(x, stride=2, resample_type='down', trim_or_pad='pad'):
+  """Resample by 'space_to_depth' conversion of time and channels (ddsp/training/nn.py:615-675).
+
+    Downsampling: [batch, time, ch] --> [batch, time/stride, ch*stride]
+    Upsampling:   [batch, time, ch] --> [batch, time*stride, ch/stride]
+
+  A pad or a trim and a reshape: framework ops on the tensor's own device (host tensors too), differentiable by themselves.  As in
+  the reference, anything but 'pad' trims - the end of time going down, the last channels going up.
+
+  Args:
+    x: [batch, time, ch] or [batch, time, 1, ch].
+    stride: Amount to resample by.
+    resample_type: 'up' or 'down'.
+    trim_or_pad: 'trim' or 'pad'. What to do if time or channels cannot be evenly divided by stride.
+
+  Returns:
+    A resampled tensor, of x's rank.
+  """
+  x = torch.as_tensor(x)
+  is_4d = x.dim() == 4
+  if is_4d:
+    x = x[:, :, 0, :]
+  n_time, n_ch = x.shape[1], x.shape[2]
+  if resample_type == 'down':
+    if trim_or_pad == 'pad':
+      pad = (stride - n_time % stride) % stride
+      x = torch.nn.functional.pad(x, (0, 0, 0, pad)) if pad > 0 else x
+    else:
+      trim = n_time % stride
+      x = x[:, :-trim, :] if trim > 0 else x
+    n_time = x.shape[1]
+    x_reshape = x.reshape(-1, n_time // stride, n_ch * stride)
+  elif resample_type == 'up':
+    if trim_or_pad == 'pad':
+      pad = (stride - n_ch % stride) % stride
+      x = torch.nn.functional.pad(x, (0, pad)) if pad > 0 else x
+    else:
+      trim = n_ch % stride
+      if trim > 0:
+        x = x[:, :, :-trim]
+    n_ch = x.shape[2]
+    x_reshape = x.reshape(-1, n_time * stride, n_ch // stride)
+  else:
+    raise ValueError('`resample_type` must be either "up" or "down"')
+  return x_reshape[:, :, None, :] if is_4d else x_reshape
+
+
+class PolyphaseResample(torch.nn.Module):
+  """Resample by interleaving time and channels (ddsp/training/nn.py:679-694)."""
+
+  def __init__(self, stride=2, resample_type='down', trim_or_pad='pad'):
+    super().__init__()
+    self.stride = stride
+    self.resample_type = resample_type
+    self.trim_or_pad = trim_or_pad
+
+  def forward(self, x):
+    return polyphase_resample(x, self.stride, self.resample_type, self.trim_or_pad)
+
+
 # ------------------ Dilated convolutions --------------------------------------
 _conv_ws = core.Workspace()
 
@@ -1765,3 +1865,207 @@ class ResNet(torch.nn.Module):
       l_in = [x, z] if is_cond else x
       x = layer(l_in)
     return x
+
+
+# ------------------ Vector Quantization ---------------------------------------
+_vq_ws = core.Workspace()
+
+
+def _vq_entry(name):
+  return _lib.vq_entry(_lib.load(), name)
+
+
+def _vq_shapes(op, x_shape, num_heads, k):
+  """-> (rows, dims) of x [..., depth] cut into num_heads vectors of `dims` per row; the errors of the vector quantizer."""
+  num_heads, k = int(num_heads), int(k)
+  if len(x_shape) < 1 or x_shape[-1] < 1:
+    raise ValueError('{}: x must be [..., depth] with depth >= 1, got {}'.format(op, tuple(x_shape)))
+  if num_heads < 1 or k < 1:
+    raise ValueError('{}: k and num_heads must be at least 1, got k = {}, num_heads = {}'.format(op, k, num_heads))
+  if x_shape[-1] % num_heads != 0:
+    raise ValueError('Input depth must be a multiple of the number of heads.')
+  rows, dims = math.prod(x_shape[:-1]), x_shape[-1] // num_heads
+  if k > _lib.VQ_MAX_CENTROIDS or dims > _lib.VQ_MAX_DIMS:
+    raise NotImplementedError('{}: at most {} centroids of {} dims per head on the MI355X path, got k = {}, depth / num_heads = {}'
+                              .format(op, _lib.VQ_MAX_CENTROIDS, _lib.VQ_MAX_DIMS, k, dims))
+  if rows * num_heads >= 2 ** 31:
+    raise NotImplementedError('{}: rows * num_heads must stay below 2 ** 31, got rows = {}, num_heads = {}'.format(op, rows, num_heads))
+  return rows, dims
+
+
+def vq_assign(x, e, num_heads=1):
+  """The nearest centroid of every vector of x, and that centroid (ddsp/training/nn.py:1417-1431), in fused kernels
+  (csrc/vq.hip; C ABI csrc/vq_abi.h): no [n, k] distance matrix exists.
+
+  Row i of x holds num_heads vectors x[i, h * D : (h + 1) * D], D = depth / num_heads, read in place.  c is the argmin over j of
+  |e_j|^2 / 2 - x . e_j, which is the argmin of the distance; of exactly equal scores the LOWEST index wins, as tf.argmin decides
+  (identical centroids have identical score bits).  k in multiples of 16 runs on the matrix cores (fp16 hi / lo operands, every
+  vector behind its own power-of-two scale), every other k on the vector ALU.  The same bits on every run, for a row alone and
+  inside any batch.  A vector with a non-finite entry gets c = 0; z_q is NaN where x is not finite.
+
+  Args:
+    x: [..., depth], of any rank >= 1, layout or dtype.
+    e: The centroids, [k, depth / num_heads].
+    num_heads: Vectors per row of x.
+
+  Returns:
+    (z_q, c): z_q of x's shape, e[c] bit for bit; c int64 [..., num_heads].  Not differentiable.
+
+  Raises:
+    ValueError: shapes that do not fit.
+    NotImplementedError: beyond the limits of the MI355X path - k <= 4096, depth / num_heads <= 512, rows * num_heads < 2 ** 31.
+  """
+  shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(torch.as_tensor(x).shape)
+  e_shape = tuple(e.shape) if hasattr(e, 'shape') else tuple(torch.as_tensor(e).shape)
+  if len(e_shape) != 2:
+    raise ValueError('vq_assign: e must be [k, depth / num_heads], got {}'.format(e_shape))
+  num_heads = int(num_heads)
+  rows, dims = _vq_shapes('vq_assign', shape, num_heads, e_shape[0])
+  if e_shape[1] != dims:
+    raise ValueError('vq_assign: e must be [k, depth / num_heads] = [k, {}], got {}'.format(dims, e_shape))
+  x, e = core.tf_float32(x).detach(), core.tf_float32(e).detach()
+  k = e_shape[0]
+  z = torch.empty_like(x)
+  c = torch.empty((rows, num_heads), dtype=torch.int32, device=x.device)
+  if rows:
+    ws = _vq_ws.get(_vq_entry('ddsp_vq_workspace_bytes')(k, dims), x.device)
+    rc = _vq_entry('ddsp_vq_assign_f32')(x.data_ptr(), e.data_ptr(), c.data_ptr(), z.data_ptr(), ws.data_ptr(), ws.numel(), rows, num_heads,
+                                         k, dims, core._stream())
+    _lib.check(rc, 'ddsp_vq_assign_f32')
+  return z, c.to(torch.int64).reshape(shape[:-1] + (num_heads,))
+
+
+def vq_statistics(x, c, k, num_heads=1):
+  """How many vectors of x each centroid was given, and their sums (ddsp/training/nn.py:1436-1438), in one kernel (csrc/vq.hip):
+  no one-hot matrix exists.  The sums are added in fp64 in the reference's x_flat order (head-major, then rows) and rounded once;
+  no atomics, the same bits on every run.  Entries of c outside [0, k) are counted nowhere.
+
+  Args:
+    x: [..., depth], of any layout or dtype.
+    c: Integer indices [..., num_heads], as vq_assign returns them.
+    k: Number of centroids.
+    num_heads: Vectors per row of x.
+
+  Returns:
+    (counts [k], sums [k, depth / num_heads]), fp32.  Not differentiable.
+  """
+  shape = tuple(x.shape) if hasattr(x, 'shape') else tuple(torch.as_tensor(x).shape)
+  num_heads, k = int(num_heads), int(k)
+  rows, dims = _vq_shapes('vq_statistics', shape, num_heads, k)
+  c = torch.as_tensor(c)
+  if tuple(c.shape) != shape[:-1] + (num_heads,) or c.is_floating_point() or c.is_complex():
+    raise ValueError('vq_statistics: c must hold integers of shape {}, got {} of {}'.format(shape[:-1] + (num_heads,), c.dtype,
+                                                                                          tuple(c.shape)))
+  x = core.tf_float32(x).detach()
+  c = c.to(device=x.device, dtype=torch.int32).contiguous()
+  counts = torch.empty((k,), dtype=torch.float32, device=x.device)
+  sums = torch.empty((k, dims), dtype=torch.float32, device=x.device)
+  rc = _vq_entry('ddsp_vq_statistics_f32')(x.data_ptr() if rows else None, c.data_ptr() if rows else None, counts.data_ptr(), sums.data_ptr(),
+                                           rows, num_heads, k, dims, core._stream())
+  _lib.check(rc, 'ddsp_vq_statistics_f32')
+  return counts, sums
+
+
+class _StraightThroughFunction(torch.autograd.Function):
+  """z_q's values with the identity as the gradient in x: the reference's x + stop_gradient(z - x) without its rounding."""
+
+  @staticmethod
+  def forward(ctx, x, z_q):
+    return z_q.view_as(z_q)
+
+  @staticmethod
+  def backward(ctx, grad_z):
+    return grad_z, None
+
+
+def _divide_no_nan(sums, counts):
+  """tf.math.divide_no_nan(sums, counts[:, None]): 0 where the count is 0."""
+  counts = counts[:, None]
+  return torch.where(counts == 0, torch.zeros_like(sums), sums / counts)
+
+
+class VectorQuantization(torch.nn.Module):
+  """Vector quantization using exponential moving average (ddsp/training/nn.py:1342-1461).
+
+  The state is two buffers under the reference's variable names, made on the first call or by build(depth): counts [k] and
+  sums [k, depth / num_heads], zeros; the centroids are e = divide_no_nan(sums, counts).  The assignment and the batch statistics
+  are vq_assign and vq_statistics (csrc/vq.hip); the centroids, the restarts and the moving averages are framework ops on [k, D].
+
+  forward(x, training=False) -> (z, c): z has the values of e[c] and the identity as its gradient in x (nothing flows into the
+  state); c is int64 [..., num_heads].  With training=True the reference's restart rule runs first - keep = counts * k >
+  restart_threshold * n, n = num_heads * rows; the r-th restarted centroid (in index order) becomes the r-th of min(restarts, n)
+  distinct uniformly drawn vectors of the batch, those beyond n take U[0, 1) values - written with fixed-shape ops (a cumulative
+  rank, randperm, rand, where: no nonzero, no host synchronisation), and afterwards counts -= (1 - gamma) (counts - batch counts),
+  the same for sums, in place.  The draws come from torch's generator, so the training call is not capturable into a graph; the
+  eval call is.
+
+  Non-finite x: c = 0 for that vector and NaN in z where x is not finite.  In training mode such a vector's NaN reaches sums
+  and from there every later call, as in the reference: outside the contract.
+  Averaging the state across data-parallel replicas (the reference's VariableAggregation.MEAN) is not built."""
+
+  def __init__(self, k, gamma=0.99, restart_threshold=0.0, num_heads=1, commitment_loss_weight=0.2, name='vector_quantization'):
+    super().__init__()
+    self.k = int(k)
+    self.gamma = gamma
+    self.restart_threshold = restart_threshold
+    self.num_heads = int(num_heads)
+    self.commitment_loss_weight = commitment_loss_weight
+    self.name = name
+    self.built = False
+
+  def build(self, depth):
+    depth = int(depth)
+    _vq_shapes('VectorQuantization', (1, depth), self.num_heads, self.k)
+    self.depth = depth
+    self.register_buffer('counts', torch.zeros((self.k,), dtype=torch.float32, device=core._device()))
+    self.register_buffer('sums', torch.zeros((self.k, depth // self.num_heads), dtype=torch.float32, device=core._device()))
+    self.built = True
+
+  def centroids(self):
+    return _divide_no_nan(self.sums, self.counts)
+
+  def _restarted(self, x, e):
+    """The centroids of a training call: those whose count has fallen to the threshold are drawn anew."""
+    heads, dims = self.num_heads, self.depth // self.num_heads
+    rows = x.numel() // self.depth
+    n = heads * rows
+    keep = self.counts * self.k > self.restart_threshold * n
+    rank = torch.cumsum((~keep).to(torch.int64), 0) - 1                  # the r-th restart, in index order
+    drawn = torch.rand((self.k, dims), dtype=torch.float32, device=x.device)
+    if n:
+      pick = torch.randperm(n, device=x.device)[rank.clamp(0, n - 1)]   # x_flat rows: distinct while rank < n
+      vectors = x.reshape(n, dims)[(pick % rows) * heads + pick // rows]        # x_flat row m = h rows + i is vector i heads + h
+      drawn = torch.where((rank < n)[:, None], vectors, drawn)
+    return torch.where(keep[:, None], e, drawn)
+
+  def forward(self, x, training=False):
+    x = core.tf_float32(x)
+    if not self.built:
+      self.build(x.shape[-1])
+    if x.shape[-1] != self.depth:
+      raise ValueError('VectorQuantization: built for depth {}, got x {}'.format(self.depth, tuple(x.shape)))
+    with torch.no_grad():
+      e = self.centroids()
+      if training:
+        e = self._restarted(x, e)
+      z_q, c = vq_assign(x, e, self.num_heads)
+      if training:
+        counts, sums = vq_statistics(x, c, self.k, self.num_heads)
+        self.counts.sub_((1 - self.gamma) * (self.counts - counts))
+        self.sums.sub_((1 - self.gamma) * (self.sums - sums))
+    z = _StraightThroughFunction.apply(x, z_q) if core._needs_grad(x) else z_q
+    return z, c
+
+  def unquantize(self, c):
+    """The centroids of the indices c [..., num_heads] -> [..., depth] (a gather of the framework's)."""
+    c = torch.as_tensor(c, device=self.sums.device)
+    return self.centroids()[c].reshape(tuple(c.shape[:-1]) + (self.depth,))
+
+  def committment_loss(self, z, z_q):
+    """Encourage encoder to output embeddings close to the current centroids."""
+    from ddsp_amd import losses
+    z_q = core.tf_float32(z_q).detach()
+    return self.commitment_loss_weight * losses.mean_difference(z, z_q, loss_type='L2')
+
+  def get_losses_dict(self, z, z_q):
+    return {self.name + '_commitment_loss': self.committment_loss(z, z_q)}
