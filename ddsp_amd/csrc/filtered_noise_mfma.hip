@@ -13,11 +13,13 @@
 // (h outside 0..127 is zero), and the second frame of the pair adds the same with a -> a - 4.  That is a
 // [16 x 160] . [160 x 16] product per pair: five v_mfma_f32_16x16x32_f16 steps.  X is Toeplitz in the noise, H is dense
 // in the taps; a lane's 8 consecutive k values are 8 consecutive samples (descending: the noise is stored reversed) and
-// 8 consecutive taps.  fp32 results come from fp16 matrix cores the way harmonic_table.hip gets them: both factors are
-// split hi + lo / 2048 and hi.hi, hi.lo + lo.hi are accumulated in fp32 (3 MFMAs per step, 15 per pair = 7.5 per
-// frame against 128 v_fma per lane and frame on the vector ALUs).  Successive pairs overlap by 128 outputs: the right
-// half of a pair's tile is shifted 8 columns (DPP row_shl:8) into the accumulator of the next pair, the left half is
-// complete and is stored.
+// 8 consecutive taps.  fp32 results come from fp16 matrix cores: both factors are cut into two fp16 parts, 22 bits each, and
+// hi.hi, hi.lo and lo.hi are accumulated in fp32 (3 MFMAs per step, 15 per pair = 7.5 per frame against 128 v_fma per lane
+// and frame on the vector ALUs).  The IR design cuts hi + lo / 2048 as harmonic_table.hip does (split_f16.h); the FIR cuts
+// its taps and its noise on ONE scale each (split_scaled: 2^13 h = hi + lo, 2^14 x = hi + lo), so that its three products add
+// up in ONE accumulator, and that accumulator - not the taps - is what moves a column between the k-steps (see the FIR
+// wavefronts).  Successive pairs overlap by 128 outputs: the right half of a pair's tile is shifted 8 columns (DPP
+// row_shl:8) into the carry of the next pair, the left half is complete and is stored.
 //
 // Alignment.  The Toeplitz operand wants 16 bytes of fp16 from an address that moves by ONE element (2 bytes) from row
 // to row.  gfx950 reads such a thing correctly (ds_read_b128 at 2-byte alignment) but ten times slower than an aligned
@@ -119,11 +121,35 @@ struct MfArgs {
 
 static __constant__ Ir65Frags kIr65Frags = make_ir65_frags();
 
+// The FIR's operands are cut on ONE scale each (split_scaled, split_f16.h): taps times 2^13, noise times 2^14, so that hi hi, hi lo
+// and lo hi add up in one accumulator and an output is acc 2^-27.
+//   noise: in (-1, 1) as it is generated, in [1/2, 1) by magnitude after the supplied rows' power-of-two normalisation: below 2^14.
+//          Every 23-bit sample (2 k - (2^23 - 1)) / 2^23 times 2^14 IS hi + lo; an 11-bit sample times 2^14 is an fp16 number.
+//   taps:  h[n] = window[n] sum_m w_m cos(..) mag[m] with exp_sigmoid magnitudes in (0, 2] (this kernel only runs with the scale
+//          fused: noise_mfma65_ok), window <= 1 and sum_m |w_m cos| <= 1 (checked below on the table itself): |h| <= 2, times 2^13
+//          is 2^14, a quarter of fp16's maximum.
+constexpr float kMfTapScale = 8192.0f;
+constexpr float kMfNoiseScale = 16384.0f;
+constexpr float kMfOutScale = 1.0f / (kMfTapScale * kMfNoiseScale);      // 2^-27
+constexpr double mf_max_tap_gain() {             // max over the taps of sum_m |w_m cos(2 pi m n / 128)|: what a tap is at most per unit magnitude
+  const Ir65Table t = make_ir65_table();
+  double worst = 0.0;
+  for (int n = 0; n <= 32; ++n) {
+    double sum = 0.0;
+    for (int i = 0; i <= 32; ++i) sum += t.c[n * kIrRowStride + i] < 0 ? -(double)t.c[n * kIrRowStride + i] : (double)t.c[n * kIrRowStride + i];
+    for (int i = 0; i < 32; ++i) sum += t.c[n * kIrRowStride + 40 + i] < 0 ? -(double)t.c[n * kIrRowStride + 40 + i] : (double)t.c[n * kIrRowStride + 40 + i];
+    worst = sum > worst ? sum : worst;
+  }
+  return worst;
+}
+static_assert(2.0 * mf_max_tap_gain() * kMfTapScale < 0.5 * 65504.0, "a scaled tap must stay far inside fp16's range");
+
 // Four taps that sit next to each other in a row of the tap table, v[0] at tap t0 (t0 a multiple of 4): split and
 // stored as two 8-byte pieces (hi part, lo part).
 __device__ __forceinline__ void mf_put4(unsigned char* hrow, int t0, float v0, float v1, float v2, float v3) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  split(v0, h0, l0); split(v1, h1, l1); split(v2, h2, l2); split(v3, h3, l3);
+  split_scaled(v0, kMfTapScale, h0, l0); split_scaled(v1, kMfTapScale, h1, l1);
+  split_scaled(v2, kMfTapScale, h2, l2); split_scaled(v3, kMfTapScale, h3, l3);
   unsigned char* q = hrow + t0 * 2;
   *reinterpret_cast<uint2*>(q) = make_uint2(pack(h0, h1), pack(h2, h3));
   *reinterpret_cast<uint2*>(q + kMfTapPlane) = make_uint2(pack(l0, l1), pack(l2, l3));
@@ -132,7 +158,8 @@ __device__ __forceinline__ void mf_put4(unsigned char* hrow, int t0, float v0, f
 // `first` is false).  t1 - 1, t1 - 2 share a dword; t1 - 3 and t1 are single halves.
 __device__ __forceinline__ void mf_put4_down(unsigned char* hrow, int t1, bool first, float v0, float v1, float v2, float v3) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  split(v0, h0, l0); split(v1, h1, l1); split(v2, h2, l2); split(v3, h3, l3);
+  split_scaled(v0, kMfTapScale, h0, l0); split_scaled(v1, kMfTapScale, h1, l1);
+  split_scaled(v2, kMfTapScale, h2, l2); split_scaled(v3, kMfTapScale, h3, l3);
   unsigned char* q = hrow + (t1 - 3) * 2;                            // taps t1-3 (odd element), then the dword (t1-2, t1-1)
   *reinterpret_cast<uint16_t*>(q) = __builtin_bit_cast(uint16_t, h3);
   *reinterpret_cast<uint16_t*>(q + kMfTapPlane) = __builtin_bit_cast(uint16_t, l3);
@@ -149,10 +176,10 @@ __device__ __forceinline__ void mf_put4_down(unsigned char* hrow, int t1, bool f
 template <bool LO>
 __device__ __forceinline__ void mf_put_quad(float4 v, int qd, unsigned char* s_xe, unsigned char* s_xo) {
   _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-  split(v.w, h0, l0);               // element u0     = sample j + 3
-  split(v.z, h1, l1);               // element u0 + 1 = sample j + 2
-  split(v.y, h2, l2);
-  split(v.x, h3, l3);
+  split_scaled(v.w, kMfNoiseScale, h0, l0);               // element u0     = sample j + 3
+  split_scaled(v.z, kMfNoiseScale, h1, l1);               // element u0 + 1 = sample j + 2
+  split_scaled(v.y, kMfNoiseScale, h2, l2);
+  split_scaled(v.x, kMfNoiseScale, h3, l3);
   const int s = qd >> 4, j = 4 * (qd & 15);
   const int u0 = 16 + kMfXStride * s + 60 - j;                     // a multiple of 4
   // copy E: dwords u0/2 and u0/2 + 1 of each plane (8 bytes, 8-byte aligned)
@@ -475,7 +502,7 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
           }
           if (mg == 0) {                                                     // tap 32 (and its mirror image, tap 96)
             _Float16 h, l;
-            split(t32, h, l);
+            split_scaled(t32, kMfTapScale, h, l);
             const uint16_t hb = __builtin_bit_cast(uint16_t, h), lb = __builtin_bit_cast(uint16_t, l);
             *reinterpret_cast<uint16_t*>(hrow + 96 * 2) = hb;              // tap 96
             *reinterpret_cast<uint16_t*>(hrow + kMfTapPlane + 96 * 2) = lb;
@@ -521,9 +548,13 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // first (g < 2) or second (g >= 2) frame, d = 8 (g & 1) + e.
     //   A (row b = i): x_frame[16 p + b - d], e = 0..7 = reversed elements u .. u + 7, u = 79 + 80 s - 16 p - b + 8 (g & 1)
     //   B (col a = i): h_row[16 (a' - p) + 8 (g & 1) + e], a' = a - 4 (second frame); zero group outside 0 <= a' - p <= 7
-    // With p = c in every lane, B of step c + 1 is B of step c moved ONE column up (a' - p - 1 is what column a - 1 had),
-    // zeros entering at column 0: only step 0 reads the tap table, steps 1 .. 4 are 8 DPP moves each (row_shr:1).  The LDS
-    // is what bounds the FIR wavefronts; this takes 8 of a pass's 30 reads and 40 % of its bytes away.
+    // With p = c in every lane, B of step c is B of step 0 moved c columns up (a' - p - c is what column a - c had), zeros
+    // entering at column 0: H_c[k][a] = H_0[k][a - c], so X_c H_c is X_c H_0 moved c columns up and the pair's tile is
+    //     D = P_0 + up(P_1 + up(P_2 + up(P_3 + up(P_4)))),      P_c = X_c H_0
+    // - Horner's rule on the ACCUMULATOR.  The tap fragment is read once per pair (step 4, the first) and never moved; between
+    // two steps the accumulator's four registers move one column up (DPP row_shr:1 within the 16 lanes of a g).  Until this was
+    // turned round the taps moved instead: 8 registers (hi and lo) per step, and three accumulators (hi hi, hi lo, lo hi), which
+    // only the lo parts' own scale of 1 / 2048 kept apart; cut on one scale (kMfTapScale) the three products share one chain.
     // Pair P = staged frames 2 P, 2 P + 1.  FIR wavefront cw walks the four pairs 4 cw .. 4 cw + 3 (unrolled: every LDS
     // address is a per-lane register plus an immediate).  In a run's first tile pair 0 only builds the carry into pair 1
     // (its own outputs belong to whoever runs the frames before) and pairs 1 .. 15 are output; in a tile that continues a
@@ -533,9 +564,14 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
     // the incomplete left half stays in registers, and the two are added and stored at the start of the NEXT tick, behind
     // the block's barrier (a warm-up pair per wavefront instead would be a fifth pass: 25 % more MFMAs and LDS reads, and
     // the LDS is what bounds this phase).
-    // ONE order of addition: every output is fma(cross, 1 / 2048, acc) + carry, the carry last, whichever way the carry
-    // came (registers, s_carry between wavefronts, s_carry between tiles): a sample's bits do not depend on where the
-    // wavefront, tile and run boundaries of its row fall, so a row filtered alone equals the same row in any batch.
+    // ONE order of addition: every output is fma(acc, 2^-27, carry), the carry last, whichever way the carry came.  Two values
+    // are scaled BEFORE their sum is taken - the right half on its way to becoming a carry, fma(acc, 2^-27, 0), and `kept`, the
+    // left half that waits a tick for its carry and is finished as kept + carry in flush_kept - and both rely on acc 2^-27 being
+    // EXACT, so that the later addition rounds once, as the fma does: every product of two fp16 numbers is a multiple of 2^-48, so a
+    // non-zero acc is at least 2^-48 and acc 2^-27 >= 2^-75 never goes subnormal.  A scale that is not a power of two, or operands
+    // that could sum below 2^-99, would break rows alone == rows in a batch here.  (The carry comes through registers, through
+    // s_carry between wavefronts or through s_carry between tiles.)  A sample's bits do not depend on where the wavefront, tile
+    // and run boundaries of its row fall, so a row filtered alone equals the same row in any batch.
     const int cw = wave - kMfPW;
     const int p_first = 4 * cw;
     f32x4 kept = {0.f, 0.f, 0.f, 0.f};      // the incomplete left half of this wavefront's first pair (cw >= 1), last tile
@@ -622,18 +658,21 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
         // after the MFMAs of step j (three steps = 18 LDS operations in flight per wavefront: the LDS only reaches its rate
         // with many operations outstanding, and two FIR wavefronts share a SIMD), the epilogue of a pair (combine, store,
         // shift the right half over) runs under the reads of the next pair.  The carry enters in the epilogue, not as
-        // the accumulator's start value, so no MFMA waits for a previous pair.
-        f16x8 fah[3], fal[3], fbh_in[2], fbl_in[2], fbh, fbl;
+        // the accumulator's start value, so no MFMA waits for a previous pair.  Within a pair the chain is move -> three MFMAs ->
+        // move; the pairs follow each other (two pairs interleaved, each move waiting for MFMAs a whole step old, measured
+        // 1.6 us per step slower at batch 128: profiles/r08_noise_fir_single_accumulator.txt - the SIMD's other wavefronts
+        // fill the wait).
+        f16x8 fah[3], fal[3], fbh[2], fbl[2];      // noise fragments: three steps in flight; tap fragments: this pair's and the next one's, never moved
         auto load_step = [&](int j, int slot) {
-          const int it = j / 5, c = j - 5 * it;
+          const int it = j / 5, c = 4 - j % 5;             // k-steps run from c = 4 DOWN to 0
           const PackedU4 qh = *reinterpret_cast<const PackedU4*>(s_x + a_hi[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
           fah[slot] = frag(qh.x, qh.y, qh.z, qh.w);
           if constexpr (!GEN_NOISE) {           // (2048-level noise is fp16 as it stands: no lo plane, no lo . hi product)
             const PackedU4 ql = *reinterpret_cast<const PackedU4*>(s_x + a_lo[it >> 1] + 32 * (4 - c) + 2 * kMfXStride * 2 * (it & 1));
             fal[slot] = frag(ql.x, ql.y, ql.z, ql.w);
           }
-          if (c == 0) {
-            // the pair's taps: first frame's row in lanes g < 2, second frame's in g >= 2
+          if (c == 4) {
+            // the pair's taps (its first step): first frame's row in lanes g < 2, second frame's in g >= 2
             const unsigned char* tr;
             if (FS64) {
               tr = s_taps + b_ptr + 2 * kMfTapRowBytes * it;
@@ -643,45 +682,46 @@ __global__ __launch_bounds__(64 * kMfWaves, 4) void noise_mfma65_kernel(
               const int row = (int)(((float)(rel0 + 128 * P + 64 * second) + 0.5f) * p.inv_fs);
               tr = s_taps + row * kMfTapRowBytes + b_off;
             }
-            fbh_in[it & 1] = *reinterpret_cast<const f16x8*>(tr);
-            fbl_in[it & 1] = *reinterpret_cast<const f16x8*>(tr + kMfTapPlane);
+            fbh[it & 1] = *reinterpret_cast<const f16x8*>(tr);
+            fbl[it & 1] = *reinterpret_cast<const f16x8*>(tr + kMfTapPlane);
           }
         };
-        // one column up (row_shr:1 within the 16 lanes of a g; column 0 receives zeros)
-        auto column_up = [](f16x8 v) {
-          typedef int i32x4 __attribute__((ext_vector_type(4)));
-          const i32x4 w = __builtin_bit_cast(i32x4, v);
-          i32x4 o;
+        // the accumulator one column up (row_shr:1 within the 16 lanes of a g; column 0 receives zeros)
+        // (through a scalar temporary: __builtin_bit_cast applied to a vector ELEMENT reads element 0 - clang 22)
+        auto column_up = [](f32x4 v) {
+          f32x4 o;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const int t = w[k];                // (a scalar temporary: see the carry below)
-            o[k] = __builtin_amdgcn_update_dpp(0, t, 0x111, 0xF, 0xF, true);
+            const float t = v[k];
+            o[k] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x111, 0xF, 0xF, true));
           }
-          return __builtin_bit_cast(f16x8, o);
+          return o;
         };
         load_step(0, 0);
         load_step(1, 1);
         load_step(2, 2);
         __builtin_amdgcn_sched_barrier(0);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_hl = {0.f, 0.f, 0.f, 0.f}, acc_lh = {0.f, 0.f, 0.f, 0.f};   // three independent chains
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};          // ONE chain per pair
         auto pipeline = [&](auto interior_tag) {
           constexpr bool kInterior = decltype(interior_tag)::value;
 #pragma unroll
           for (int j = 0; j < 20; ++j) {
-            const int it = j / 5, c = j - 5 * it, slot = j % 3;
-            if (c == 0) { fbh = fbh_in[it & 1]; fbl = fbl_in[it & 1]; }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah[slot], fbh, acc, 0, 0, 0);
-            acc_hl = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah[slot], fbl, acc_hl, 0, 0, 0);
-            if constexpr (!GEN_NOISE) acc_lh = __builtin_amdgcn_mfma_f32_16x16x32_f16(fal[slot], fbh, acc_lh, 0, 0, 0);
+            const int it = j / 5, c = 4 - j % 5, slot = j % 3;
+            // Horner's rule: what the steps above c have summed moves one column up, then step c's three products join it -
+            // hi hi, hi lo and LAST lo hi (supplied noise without lo parts then adds exact zeros behind what Gen11 computes)
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+            if (c < 4) a = column_up(acc);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah[slot], fbh[it & 1], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(fah[slot], fbl[it & 1], a, 0, 0, 0);
+            if constexpr (!GEN_NOISE) a = __builtin_amdgcn_mfma_f32_16x16x32_f16(fal[slot], fbh[it & 1], a, 0, 0, 0);
+            acc = a;
             __builtin_amdgcn_sched_barrier(0);
             if (j + 3 < 20) load_step(j + 3, slot);
-            if (c < 4) { fbh = column_up(fbh); fbl = column_up(fbl); }      // under the MFMAs
             __builtin_amdgcn_sched_barrier(0);
-            if (c == 4) {
-              const f32x4 comb = combine(acc, acc_hl + acc_lh) + carry;          // the carry last: see above
-              acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-              acc_hl = (f32x4){0.f, 0.f, 0.f, 0.f};
-              acc_lh = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (c == 0) {
+              f32x4 comb;                                                          // the carry last: see above
+#pragma unroll
+              for (int r = 0; r < 4; ++r) { const float v = a[r], cr = carry[r]; comb[r] = __builtin_fmaf(v, kMfOutScale, cr); }
               // D[row b = 4 g + r][col a = i]: columns 0..7 are complete (the first pair's: see above)
               if (it == 0) kept = comb;
               if (mi < 8 && (it > 0 || first_direct)) {

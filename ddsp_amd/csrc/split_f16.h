@@ -24,6 +24,17 @@ __device__ __forceinline__ void split(float v, _Float16& hi, _Float16& lo) {
   hi = (_Float16)v;
   lo = (_Float16)((v - (float)hi) * kLoScale);
 }
+// The same 22 bits cut so that BOTH parts sit on one scale: s v = hi + lo, s a power of two that brings the data near the top of
+// fp16's range (the caller's to choose, and to bound: s |v| must stay below 65504).  hi hi, hi lo and lo hi then add up in ONE
+// fp32 accumulator and the product is acc / (s_a s_b) - noise_mfma65_kernel's FIR, whose accumulator moves between k-steps.
+// lo is at most half a unit of hi's last place: below s |v| = 2^-3 it is an fp16 subnormal (below 2^-25: zero).  gfx950's matrix
+// cores take subnormal inputs as they are: tests/test_gpu_noise_single_accumulator.py holds the kernel to a bound that operands
+// with flushed lo parts miss ninefold.
+__device__ __forceinline__ void split_scaled(float v, float s, _Float16& hi, _Float16& lo) {
+  const float t = v * s;
+  hi = (_Float16)t;
+  lo = (_Float16)(t - (float)hi);
+}
 __device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
